@@ -15,7 +15,14 @@ the loop's own window rule, NNG:145,152).  It is a lower bound of the reference'
 value depends on nr_cores through the chunk-local seed dictionary, NNG:112,125-129), is identical for the CPU
 baseline and the GPU, and is computable from the result alone.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the steps and prints the headline line (metric, value, unit, higher_is_better, dtype,
+ms_per_step = wall milliseconds of one timed step, and the workload's config with the graph's digest).  --dump-outputs DIR also writes
+the graph of the last timed step (best, row_ptr, cols: what store.nn_graph returns) as DIR/<name>.npy in float64.
+
+--full adds everything else: the fixture checks of the default workload (the graph, and with the extras the 2-set graph and the
+alignments, against the reference-loop / oracle digests; exit status 1 on a mismatch), per_rank_kernel_ms / protocol_ms, and these
+objects on the JSON line (--no-cpu-baseline leaves out cpu_baseline; --no-extras the untimed extras: wrappers, other_kernels,
+two_set_graph and their rooflines):
   roofline      dominant kernel k_qgram_mm (q-gram lower bounds of every pair of the length window as a banded A B^T on the matrix cores,
                 fp4 MFMA): `achieved` = algorithmic flops (tiles x 65 536 pairs x K x 2) / the kernel's own HIP-event time of THIS run, against
                 the dense fp4 peak; `traffic` = PMC bytes (2 x FETCH_SIZE + WRITE_SIZE) of the dispatch from profiles/counters.json, which
@@ -78,6 +85,22 @@ def graph_digest(best, row_ptr, cols):
     for x, t in ((best, np.int32), (row_ptr, np.int64), (cols, np.uint32)):
         h.update(np.ascontiguousarray(x, dtype=t).tobytes())
     return h.hexdigest()
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, arrays):
+    """{name: 1-d integer array} -> path/<name>.npy as float64 (exact for integers below 2^53), at most DUMP_LIMIT_BYTES in all.  An
+    array longer than its share is written as a fixed sample: sorted positions drawn with PCG64(0), a function of its length only, so
+    that two builds which computed arrays of the same length are compared at the same positions."""
+    os.makedirs(path, exist_ok=True)
+    share = (DUMP_LIMIT_BYTES - 256 * len(arrays)) // (8 * len(arrays))          # (256: room for each file's .npy header)
+    for name, x in arrays.items():
+        x = np.asarray(x).ravel()
+        if len(x) > share:
+            x = x[np.sort(np.random.Generator(np.random.PCG64(0)).choice(len(x), share, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), x.astype(np.float64))
 
 
 _H1, _H2, _H3 = np.uint64(0xD6E8FEB86659FD93), np.uint64(0x9E3779B97F4A7C15), np.uint64(0xC2B2AE3D27D4EB4F)
@@ -399,10 +422,15 @@ def main():
     ap.add_argument("--length", type=int, default=2500)
     ap.add_argument("--isoforms", type=int, default=10)
     ap.add_argument("--seed", type=int, default=30001)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed extras (other kernels, wrappers)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline figure: CPU baselines, roofline, per-rank kernel times, the untimed extras and the fixture checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the graph of the last timed step as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the untimed extras (other kernels, wrappers)")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)
@@ -424,7 +452,7 @@ def main():
     # CPU baseline first: its fork()ed workers must exist (and be gone) before this process touches the GPU
     cpu = None
     cpu_pool = None
-    if rank == 0 and not args.no_cpu_baseline:          # (rank 0 of any world size; the others wait at the first barrier)
+    if args.full and rank == 0 and not args.no_cpu_baseline:          # (rank 0 of any world size; the others wait at the first barrier)
         if world == 1 and not args.no_extras and (args.reads, args.length, args.isoforms, args.seed) == (50000, 2500, 10, 30001):
             try:          # the 2-set leg's inputs, for the workers forked below (cpu_two_set)
                 _X, _C, _merged, _z, _mod = two_set_inputs()
@@ -494,28 +522,112 @@ def main():
     all_ms = phase_ms["kernel_ms"]
     sync()
     dt = time.perf_counter() - t0
-    per_rank_kernel_ms = [float(np.mean(all_ms))]
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device=red_device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-        km = torch.tensor([float(np.mean(all_ms))], dtype=torch.float64, device=red_device)
-        kms = [torch.zeros_like(km) for _ in range(world)]
-        dist.all_gather(kms, km)
-        per_rank_kernel_ms = [float(x.item()) for x in kms]
     ms_per_step = dt / args.steps * 1e3
     n_align = window_pairs(lens, last["best"])
     value = n_align / (ms_per_step / 1e3)
+    is_default = (args.reads, args.length, args.isoforms, args.seed) == (50000, 2500, 10, 30001)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"best": last["best"], "row_ptr": last["row_ptr"], "cols": last["cols"]})
 
-    # ---- roofline of the dominant kernel on this rank --------------------------------------------------------------
+    result = {
+        "metric": "read x candidate alignments/sec (NN-graph build, %dk x %.1fkb reads)" % (args.reads // 1000, args.length / 1000.0),
+        "value": value, "unit": "alignments/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": "u64", "data": "synthetic",
+        "config": {"workload": ("C3: " if is_default else "custom: ") + "%d synthetic CCS reads (%d unique), ~%d bp, %d isoforms, seed %d; 1-set NN graph"
+                               % (args.reads, len(seqs), args.length, args.isoforms, args.seed),
+                   "alignments_per_step": n_align, "nn_graph_wall_ms": ms_per_step, "edges": int(last["edges"]),
+                   "median_nn_distance": float(np.median(last["best"][last["best"] >= 0])) if (last["best"] >= 0).any() else None,
+                   "graph_digest": graph_digest(last["best"], last["row_ptr"], last["cols"]),
+                   "parallelism": "1 process/GPU; pairs sharded by lower index; all_reduce(MIN)+all_gather over RCCL" if world > 1 else "single GPU"},
+        "rccl_ranks": dist.get_world_size() if dist is not None else 1,
+        "dist_backend": dist.get_backend() if dist is not None else None,
+    }
+    if args.full:
+        per_rank_kernel_ms = [float(np.mean(all_ms))]
+        if dist is not None:
+            km = torch.tensor([float(np.mean(all_ms))], dtype=torch.float64, device=red_device)
+            kms = [torch.zeros_like(km) for _ in range(world)]
+            dist.all_gather(kms, km)
+            per_rank_kernel_ms = [float(x.item()) for x in kms]
+        roofline, ctr, kk = roofline_1set(last, phase_ms, lens, is_default and world == 1)
+        result["roofline"] = roofline
+        result["per_rank_kernel_ms"] = per_rank_kernel_ms
+        # what a step costs beyond the slowest rank's kernels: host work of the phases, the reductions and the gather, waiting for the others
+        result["protocol_ms"] = ms_per_step - max(per_rank_kernel_ms)
+    if args.full and world == 1 and not args.no_extras:
+        try:
+            result["other_kernels"] = other_kernels(store, seqs, lens, last, true_isoforms, ctr if is_default else {})
+        except Exception as e:  # the headline line must still be printed
+            result["other_kernels"] = {"error": repr(e)}
+        pair_ed = []
+        sw_leg = {}
+        try:
+            result["wrappers"] = wrappers(accs, seqs_all, pair_ed, sw_leg)
+        except Exception as e:
+            result["wrappers"] = {"error": repr(e)}
+        if is_default:
+            try:
+                result["two_set_graph"] = two_set_leg()
+                result["roofline_2set"] = roofline_2set(result["two_set_graph"], kk, ctr if is_default else {})
+            except Exception as e:
+                result["two_set_graph"] = {"error": repr(e)}
+        if sw_leg:
+            result["roofline_sw"] = roofline_sw(sw_leg, ctr if is_default else {})
+            if is_default:
+                result["config"]["sw_digest"] = sw_leg["digest"]
+                result["config"]["sw_digest_expected"] = EXPECTED_SW_DIGEST_C3
+                result["config"]["alignments_equal_oracle_fixture"] = sw_leg["digest"] == EXPECTED_SW_DIGEST_C3
+        if cpu_pool is not None and "seqs2" in _G and "error" not in result.get("two_set_graph", {"error": 1}):
+            try:
+                cpu["two_set"] = cpu_two_set(cpu_pool, cpu["cores"])
+                result["two_set_graph"]["vs_cpu_baseline_wall"] = result["two_set_graph"]["alignments_per_s_wall"] / cpu["two_set"]["value"]
+            except Exception as e:
+                cpu["two_set_error"] = repr(e)
+        if cpu_pool is not None and pair_ed:
+            try:
+                cpu.update(cpu_pair_legs(cpu_pool, cpu["cores"], pair_ed))
+                w = result["wrappers"]
+                w["edlib_align_sequences_vs_cpu_baseline"] = w["edlib_align_sequences_pairs_per_s"] / cpu["ed_pairs"]["value"]
+                w["sw_align_sequences_vs_cpu_baseline"] = w["sw_align_sequences_pairs_per_s"] / cpu["sw_pairs"]["value"]
+            except Exception as e:
+                cpu["pair_legs_error"] = repr(e)
+    if cpu_pool is not None:
+        cpu_pool.close()
+        cpu_pool.join()
+    if cpu is not None:
+        result["cpu_baseline"] = cpu
+        result["speedup_vs_cpu_baseline"] = value / cpu["value"] if cpu["value"] else None
+    if args.full and is_default:
+        result["config"]["graph_digest_expected"] = EXPECTED_GRAPH_DIGEST_C3
+        result["config"]["graph_equals_reference_loop_fixture"] = result["config"]["graph_digest"] == EXPECTED_GRAPH_DIGEST_C3
+    if rank == 0:
+        print(json.dumps(result))
+    if dist is not None:
+        dist.destroy_process_group()
+    if args.full and is_default and result["config"]["graph_digest"] != EXPECTED_GRAPH_DIGEST_C3:
+        raise SystemExit("bench.py: the graph of the default workload has digest %s, the reference-loop fixture %s: the result is WRONG, the line above is not a measurement"
+                         % (result["config"]["graph_digest"], EXPECTED_GRAPH_DIGEST_C3))
+    if is_default and result.get("two_set_graph", {}).get("every_row_equals_reference_loop_fixture") is False:
+        raise SystemExit("bench.py: the 2-set graph of the default workload's reads against the g19 candidates differs from the reference-loop fixture: the two_set_graph leg is WRONG")
+    if is_default and result["config"].get("alignments_equal_oracle_fixture") is False:
+        raise SystemExit("bench.py: the alignments of the default workload's partition pairs have digest %s, the oracle fixture %s: the wrappers leg is WRONG"
+                         % (result["config"]["sw_digest"], EXPECTED_SW_DIGEST_C3))
+
+
+def roofline_1set(last, phase_ms, lens, use_ctr):
+    """Roofline of the dominant kernel of the timed steps on this rank and where their kernel time goes (HIP events of the steps;
+    use_ctr: the committed PMC figures of profiles/counters.json apply -- default workload on one GPU): (roofline, counters, K)"""
     st0 = {k: sum(x.get(k, 0) for x in last["stats"]) for k in ("pairs_evaluated", "cells_columns", "pairs_prefiltered", "pairs_lanes", "bound_tiles",
                                                                  "narrow_columns", "pairs_narrow", "pairs_block_rejected")}   # this rank, all phases
     pairs_eval = int(st0["pairs_evaluated"])
     mean_len = float(lens.mean())
     pm = {k: (float(np.mean(v)) if v else 0.0) for k, v in phase_ms.items()}
-    is_default = (args.reads, args.length, args.isoforms, args.seed) == (50000, 2500, 10, 30001)
     ctr, ctr_note = load_counters()
-    use_ctr = is_default and world == 1          # the committed PMC figures belong to the default workload on one GPU
 
     def valu_frac(key, ms):
         c = ctr.get(key, {})
@@ -594,83 +706,7 @@ def main():
                                 "GBps": alg_bytes / (align_ms / 1e3) / 1e9 if align_ms > 0 else None,
                                 "note": "SURVEY 8(d) byte model x pairs aligned / alignment kernel time; NOT a physical rate: of the reference's alignments (config.alignments_per_step) "
                                         "all but these are decided by the two lower bounds and never aligned"}}
-
-    result = {
-        "metric": "read x candidate alignments/sec (NN-graph build, %dk x %.1fkb reads)" % (args.reads // 1000, args.length / 1000.0),
-        "value": value, "unit": "alignments/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-        "dtype": "u64", "data": "synthetic",
-        "config": {"workload": ("C3: " if is_default else "custom: ") + "%d synthetic CCS reads (%d unique), ~%d bp, %d isoforms, seed %d; 1-set NN graph"
-                               % (args.reads, len(seqs), args.length, args.isoforms, args.seed),
-                   "alignments_per_step": n_align, "nn_graph_wall_ms": ms_per_step, "edges": int(last["edges"]),
-                   "median_nn_distance": float(np.median(last["best"][last["best"] >= 0])) if (last["best"] >= 0).any() else None,
-                   "graph_digest": graph_digest(last["best"], last["row_ptr"], last["cols"]),
-                   "parallelism": "1 process/GPU; pairs sharded by lower index; all_reduce(MIN)+all_gather over RCCL" if world > 1 else "single GPU"},
-        "roofline": roofline,
-        "rccl_ranks": dist.get_world_size() if dist is not None else 1,
-        "dist_backend": dist.get_backend() if dist is not None else None,
-        "per_rank_kernel_ms": per_rank_kernel_ms,
-        # what a step costs beyond the slowest rank's kernels: host work of the phases, the reductions and the gather, waiting for the others
-        "protocol_ms": ms_per_step - max(per_rank_kernel_ms),
-    }
-    if world == 1 and not args.no_extras:
-        try:
-            result["other_kernels"] = other_kernels(store, seqs, lens, last, true_isoforms, ctr if is_default else {})
-        except Exception as e:  # the headline line must still be printed
-            result["other_kernels"] = {"error": repr(e)}
-        pair_ed = []
-        sw_leg = {}
-        try:
-            result["wrappers"] = wrappers(accs, seqs_all, pair_ed, sw_leg)
-        except Exception as e:
-            result["wrappers"] = {"error": repr(e)}
-        if is_default:
-            try:
-                result["two_set_graph"] = two_set_leg()
-                result["roofline_2set"] = roofline_2set(result["two_set_graph"], kk, ctr if is_default else {})
-            except Exception as e:
-                result["two_set_graph"] = {"error": repr(e)}
-        if sw_leg:
-            result["roofline_sw"] = roofline_sw(sw_leg, ctr if is_default else {})
-            if is_default:
-                result["config"]["sw_digest"] = sw_leg["digest"]
-                result["config"]["sw_digest_expected"] = EXPECTED_SW_DIGEST_C3
-                result["config"]["alignments_equal_oracle_fixture"] = sw_leg["digest"] == EXPECTED_SW_DIGEST_C3
-        if cpu_pool is not None and "seqs2" in _G and "error" not in result.get("two_set_graph", {"error": 1}):
-            try:
-                cpu["two_set"] = cpu_two_set(cpu_pool, cpu["cores"])
-                result["two_set_graph"]["vs_cpu_baseline_wall"] = result["two_set_graph"]["alignments_per_s_wall"] / cpu["two_set"]["value"]
-            except Exception as e:
-                cpu["two_set_error"] = repr(e)
-        if cpu_pool is not None and pair_ed:
-            try:
-                cpu.update(cpu_pair_legs(cpu_pool, cpu["cores"], pair_ed))
-                w = result["wrappers"]
-                w["edlib_align_sequences_vs_cpu_baseline"] = w["edlib_align_sequences_pairs_per_s"] / cpu["ed_pairs"]["value"]
-                w["sw_align_sequences_vs_cpu_baseline"] = w["sw_align_sequences_pairs_per_s"] / cpu["sw_pairs"]["value"]
-            except Exception as e:
-                cpu["pair_legs_error"] = repr(e)
-    if cpu_pool is not None:
-        cpu_pool.close()
-        cpu_pool.join()
-    if cpu is not None:
-        result["cpu_baseline"] = cpu
-        result["speedup_vs_cpu_baseline"] = value / cpu["value"] if cpu["value"] else None
-    if is_default:
-        result["config"]["graph_digest_expected"] = EXPECTED_GRAPH_DIGEST_C3
-        result["config"]["graph_equals_reference_loop_fixture"] = result["config"]["graph_digest"] == EXPECTED_GRAPH_DIGEST_C3
-    if rank == 0:
-        print(json.dumps(result))
-    if dist is not None:
-        dist.destroy_process_group()
-    if is_default and result["config"]["graph_digest"] != EXPECTED_GRAPH_DIGEST_C3:
-        raise SystemExit("bench.py: the graph of the default workload has digest %s, the reference-loop fixture %s: the result is WRONG, the line above is not a measurement"
-                         % (result["config"]["graph_digest"], EXPECTED_GRAPH_DIGEST_C3))
-    if is_default and result.get("two_set_graph", {}).get("every_row_equals_reference_loop_fixture") is False:
-        raise SystemExit("bench.py: the 2-set graph of the default workload's reads against the g19 candidates differs from the reference-loop fixture: the two_set_graph leg is WRONG")
-    if is_default and result["config"].get("alignments_equal_oracle_fixture") is False:
-        raise SystemExit("bench.py: the alignments of the default workload's partition pairs have digest %s, the oracle fixture %s: the wrappers leg is WRONG"
-                         % (result["config"]["sw_digest"], EXPECTED_SW_DIGEST_C3))
+    return roofline, ctr, kk
 
 
 def _fracs(ctr, key, ms, own_time=False):

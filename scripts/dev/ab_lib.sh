@@ -1,7 +1,7 @@
 # scripts/dev/ab_lib.sh NAME : bench.py's NN-graph step with the shipped library and with isocon_amd/lib/libisocon_hip_NAME.so (scripts/dev/build_variant.sh), twice each
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
-run() { name=$1; shift; env "$@" python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+run() { name=$1; shift; env "$@" python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import json,sys
 for ln in sys.stdin:
     if ln.startswith('{'):

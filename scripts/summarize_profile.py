@@ -1,4 +1,4 @@
-"""Turn gpurun_out/{prof,pmc_sq,pmc_fetch,pmc_write}_<TAG> (written by scripts/profile_bench.sh) into the tracked files
+"""Turn $PROFILE_OUT/{prof,pmc_sq,pmc_fetch,pmc_write}_<TAG> (default profile_out/; written by scripts/profile_bench.sh) into the tracked files
 profiles/<TAG>_kernel_stats.csv, profiles/<TAG>_pmc_summary.txt, profiles/<TAG>_sq_summary.txt, profiles/<TAG>_bench.json and
 profiles/counters.json (read by bench.py: per-dispatch SQ_INSTS_VALU and HBM bytes of the kernels its line reports)."""
 import csv, glob, json, os, shutil, sys
@@ -7,7 +7,7 @@ if __name__ != "__main__" or len(sys.argv) < 2:          # a script that rewrite
     raise SystemExit("usage: python scripts/summarize_profile.py <TAG>")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1]
-out = os.path.join(ROOT, "gpurun_out")
+out = os.path.join(ROOT, os.environ.get("PROFILE_OUT", "profile_out"))
 prof = os.path.join(ROOT, "profiles")
 
 
@@ -124,7 +124,7 @@ def classify(rows):
 sq, fetch, write = dispatches("sq"), dispatches("fetch"), dispatches("write")
 sys.path.insert(0, ROOT)
 import bench as _bench                      # source_digest(): the kernel sources these counters belong to
-counters = {"round": tag, "source_digest": _bench.source_digest(), "command": "rocprofv3 --pmc <counters> --kernel-trace -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline "
+counters = {"round": tag, "source_digest": _bench.source_digest(), "command": "rocprofv3 --pmc <counters> --kernel-trace -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline "
                                      "(three passes: SQ_*, FETCH_SIZE, WRITE_SIZE)", "workload": "C3 (50k x 2.5kb, seed 30001)"}
 lines = [counters["command"], "dispatches of one NN-graph step at C3 (50k x 2.5kb) and of bench.py's untimed extras"]
 for kind, rows in (("sq", sq), ("fetch", fetch), ("write", write)):

@@ -102,6 +102,24 @@ def test_bench_window_pairs_numerator():
     assert bench.window_pairs(lens, best) == 2 + 1 + 3 + 0 + 4
 
 
+def test_bench_dump_outputs_exact_and_capped(tmp_path, monkeypatch):
+    import bench
+    best = np.array([3, -1, 0, 2 ** 31 - 1], dtype=np.int32)
+    cols = np.arange(5000, dtype=np.uint32) * 7
+    bench.dump_outputs(str(tmp_path / "a"), {"best": best, "cols": cols})
+    for name, x in (("best", best), ("cols", cols)):
+        y = np.load(tmp_path / "a" / (name + ".npy"))
+        assert y.dtype == np.float64 and (y == x).all()
+    # over the limit: a seeded sample, the same positions on every call, within the limit in all
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 8 * 1000 + 2 * 256)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"best": best, "cols": cols})
+    y = np.load(tmp_path / "b" / "cols.npy")
+    assert len(y) == 500 and (np.diff(y) > 0).all() and np.isin(y, cols).all()
+    assert (y == np.load(tmp_path / "c" / "cols.npy")).all() and len(np.load(tmp_path / "b" / "best.npy")) == 4
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= bench.DUMP_LIMIT_BYTES
+
+
 def test_synth_is_deterministic():
     from isocon_amd import synth
     a = synth.make_reads(50, 300, 3, seed=5)

@@ -18,7 +18,7 @@ def _bench(n_gpus, extra_env, workload=("--reads", "6000", "--length", "1200", "
     env = dict(os.environ)
     env.update(extra_env)
     env.pop("RANK", None); env.pop("WORLD_SIZE", None); env.pop("LOCAL_RANK", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n_gpus), "--steps", "1", "--warmup", str(warmup), "--no-cpu-baseline", "--no-extras"] + list(workload)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n_gpus), "--steps", "1", "--warmup", str(warmup), "--full", "--no-cpu-baseline", "--no-extras"] + list(workload)
     out = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
