@@ -135,17 +135,17 @@ typedef struct {
     uint64_t tiles;               /* 64-lane tiles executed */
     uint64_t hits;                /* candidate edges recorded on the device */
     uint64_t fallback_queries;    /* queries that needed a band wider than 64 rows */
-    uint64_t full_pairs;          /* pairs sent to the un-banded kernel */
+    uint64_t full_pairs;          /* pairs sent to the un-banded kernel (filled by the depth-limited 2-set search as well) */
     float kernel_ms;              /* HIP-event time of all kernels of the call */
     float scan_kernel_ms;         /* ... of the dominant kernel launch (64-row band scan, main pass) */
     float seed_kernel_ms;         /* ... of the seed pass that precedes it (1-set only) */
-    uint32_t scan_launches;       /* launches summed into scan_kernel_ms */
+    uint32_t scan_launches;       /* launches summed into scan_kernel_ms; depth-limited 2-set search: the number of rounds (see isocon_nn_graph) */
     uint64_t pairs_prefiltered;   /* pairs of the main pass whose q-gram bound exceeded their threshold (never aligned) */
     float bound_kernel_ms;        /* HIP-event time of the q-gram profile + bound kernels (part of kernel_ms) */
     float list_kernel_ms;         /* ... of the kernel that collects the survivors of the bounds into lists (part of kernel_ms) */
     float lanes_kernel_ms;        /* ... of the one-pair-per-lane launch of the main pass (entries with few pairs; NOT in scan_kernel_ms) */
     float narrow_kernel_ms;       /* of scan_kernel_ms: the table launch over the pairs whose threshold is <= 31 (32-row form of the kernel) */
-    uint64_t pairs_lanes;         /* pairs of the main pass aligned one pair per lane (the rest went through tables) */
+    uint64_t pairs_lanes;         /* pairs of the main pass aligned one pair per lane (the rest went through tables); depth-limited 2-set search: see isocon_nn_graph */
     uint64_t bound_tiles;         /* 256 x 256 tiles of the bound matrix computed (each: 65 536 pairs x isocon_qgram_params() multiply-adds) */
     uint64_t pairs_wide_to_lanes; /* of pairs_lanes: pairs with a threshold above 31 sent there because of it (ISOCON_DEBUG_VARIANT=nn_narrow=1 only) */
     uint64_t narrow_columns;      /* of cells_columns: columns run by the 32-row form of the table kernel */
@@ -164,7 +164,11 @@ typedef struct {
  *     get_exact_nearest_neighbor_graph (:19-82) independent of nr_cores.
  *   2-set (is_target != NULL): queries are the entries with is_target[i] == 0, neighbours only entries with
  *     is_target[i] == 1, distance 0 admitted == get_nearest_neighbors_2set (:341-424).
- *     depth must be >= the number of targets (the reference's default 2**32 never binds).
+ *     depth >= the number of targets (the reference's default 2**32) never binds.  A smaller depth is the reference's rule (:416): a
+ *     read stops after the iteration in which its count of candidate alignments reaches depth (depth + 1 alignments at most, depth 0 =
+ *     one iteration), candidates visited by ascending offset, the lower one first -- carried out on the device round by round.
+ *     stats on that path: kernel_ms, hits, pairs_lanes = distinct (read, candidate) pairs whose distance was asked for, full_pairs,
+ *     pairs_bytes, scan_launches = rounds.
  * Output CSR: out_best[i] = minimal distance (-1 if row empty), out_row_ptr[n+1], out_cols = neighbour indices in
  * the reference's insertion order (ascending offset, lower index first).  If the edges do not fit cols_cap the
  * call returns ISOCON_E_CAPACITY and *n_cols_needed holds the required capacity.

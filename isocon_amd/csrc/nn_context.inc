@@ -26,6 +26,7 @@ struct NNContext {
     uint32_t n = 0;
     std::vector<uint8_t> qflag, tflag;
     bool two_set = false;
+    bool depth_binds = false;            // 2-set: neighbor_search_depth is smaller than the number of targets
     std::vector<uint8_t> wide_mask;      // phase B in sub-steps (sharded callers): the queries of the whole phase, fixed at its start (empty: derived from best[])
     int32_t min_d = 1;
     uint32_t depth = 0x7fffffffu;
@@ -284,7 +285,7 @@ void length_window(const std::vector<int32_t> &lens, uint32_t x, int32_t w, uint
 }
 
 int nn_setup(NNContext &C, isocon_store *s, const uint8_t *is_converged, const uint8_t *is_target, uint64_t depth,
-             const int32_t *best_in)
+             const int32_t *best_in, bool depth_walk = false)
 {
     C.st = s;
     C.n = s->dev.n;
@@ -304,8 +305,10 @@ int nn_setup(NNContext &C, isocon_store *s, const uint8_t *is_converged, const u
         else { C.tflag[i] = 1; C.qflag[i] = (is_converged && is_converged[i]) ? 0 : 1; }
     }
     if (C.two_set) {
-        // NNG:416 stops after `depth` candidate alignments (an order-dependent rule); exact only when it cannot bind
-        if (depth < n_targets) { g_last_error = "2-set search with neighbor_search_depth < number of targets is not supported"; return ISOCON_E_UNSUPPORTED; }
+        // NNG:416 stops after `depth` candidate alignments (an order-dependent rule): the passes of this context are exact only when it
+        // cannot bind.  depth_walk: the caller (isocon_nn_graph) sends such a call through nn2_depth_graph, which carries the rule out.
+        C.depth_binds = depth < n_targets;
+        if (C.depth_binds && !depth_walk) { g_last_error = "2-set search with neighbor_search_depth < number of targets is not supported"; return ISOCON_E_UNSUPPORTED; }
         C.depth = 0x7fffffffu;
     } else {
         if (depth == 0) { g_last_error = "neighbor_search_depth must be >= 1"; return ISOCON_E_ARG; }

@@ -65,6 +65,10 @@ int nn_finalize_device(isocon_store *st, uint32_t n, const int32_t *best, const 
     return nn_finalize_device_core(pl, n, d_best.as<int32_t>(), best, d_hits.as<int32_t>(), n_hits, out_best, out_row_ptr, out_cols, cols_cap, n_cols_needed);
 }
 
+// the depth-limited reads x candidates search (nn2_depth.inc)
+int nn2_depth_graph(NNContext &C, uint64_t depth, int32_t *out_best, uint64_t *out_row_ptr, uint32_t *out_cols, uint64_t cols_cap,
+                    uint64_t *n_cols_needed, isocon_nn_stats *stats);
+
 
 }  // namespace
 
@@ -188,10 +192,12 @@ extern "C" int isocon_nn_graph(isocon_store *s, const uint8_t *is_converged, con
     struct Total { std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
                    ~Total() { if (getenv("ISOCON_DEBUG")) fprintf(stderr, "[isocon] %-28s %8.2f ms\n", "isocon_nn_graph total", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count()); } } total;
     NNContext C;
-    int rc = nn_setup(C, s, is_converged, is_target, depth, nullptr);
+    int rc = nn_setup(C, s, is_converged, is_target, depth, nullptr, true);
     if (rc) return rc;
     clk0.lap("setup");
     if (getenv("ISOCON_DEBUG")) { (void)hipDeviceSynchronize(); clk0.lap("sync after setup"); }
+    // 2-set with a depth limit that binds: the order-dependent rule of NNG:416, round by round (ISOCON_DEBUG_VARIANT=nn_2set_walk: every 2-set call)
+    if (C.two_set && (C.depth_binds || variant("nn_2set_walk"))) return nn2_depth_graph(C, depth, out_best, out_row_ptr, out_cols, cols_cap, n_cols_needed, stats);
     C.keep_dev = n >= 1024 && !variant("nn_host_finalize");
     if ((rc = nn_phase_a(C, QMap{0u, n, 1u, 0u}, true, true, true))) return rc;
     HostClock clk;

@@ -189,55 +189,6 @@ def compute_nearest_neighbor_graph(S, has_converged, params):
     return nearest_neighbor_graph, isolated
 
 
-def _replay_2set_depth(seqs, accs, is_t, depth, st):
-    """neighbor_search_depth smaller than the number of candidates (never the case with the reference's default
-    2**32): NNG:416 stops after `depth` candidate alignments, an order-dependent rule.  Distances to the candidates
-    come from the GPU (bounded by len(read), NNG:356); the stop/depth bookkeeping of NNG:362-419 is replayed here."""
-    n = len(seqs)
-    lens = np.fromiter((len(s) for s in seqs), dtype=np.int64, count=n)
-    t_idx = np.nonzero(is_t)[0]
-    q_idx = np.nonzero(~is_t)[0]
-    a = np.repeat(q_idx, len(t_idx)).astype(np.uint32)
-    b = np.tile(t_idx, len(q_idx)).astype(np.uint32)
-    k = lens[a].astype(np.int32)
-    ed = st.ed_pairs(a, b, k).reshape(len(q_idx), len(t_idx)) if len(a) else np.zeros((len(q_idx), 0), np.int32)
-    col_of = {int(t): c for c, t in enumerate(t_idx)}
-    out = {}
-    for r, i in enumerate(q_idx.tolist()):
-        best_ed = int(lens[i])
-        cur = {}
-        stop_up = stop_down = False
-        processed = 0
-        j = 1
-        while True:
-            if i - j < 0:
-                stop_down = True
-            if i + j >= n:
-                stop_up = True
-            if not stop_down and abs(lens[i] - lens[i - j]) > best_ed:
-                stop_down = True
-            if not stop_up and abs(lens[i] - lens[i + j]) > best_ed:
-                stop_up = True
-            for side_stopped, p in ((stop_down, i - j), (stop_up, i + j)):
-                if side_stopped or not is_t[p]:
-                    continue
-                processed += 1
-                d = int(ed[r, col_of[p]])
-                d = d if 0 <= d <= best_ed else -1
-                if 0 <= d < best_ed:
-                    best_ed = d
-                    cur = {accs[p]: d}
-                elif d == best_ed:
-                    cur[accs[p]] = d
-            if stop_down and stop_up:
-                break
-            if processed >= depth:
-                break
-            j += 1
-        out[accs[i]] = cur
-    return out
-
-
 def _nn_2set(seq_to_acc_list_sorted_all, target_accessions, depth):
     seqs = [s for s, _ in seq_to_acc_list_sorted_all]
     accs = [a for _, a in seq_to_acc_list_sorted_all]
@@ -251,8 +202,11 @@ def _nn_2set_arrays(seqs, accs, is_t, depth):
         st = SeqStore(seqs)
         try:
             if depth < int(is_t.sum()):
-                return _replay_2set_depth(seqs, accs, is_t, depth, st)
-            best, row_ptr, cols, stats = _graph(st, seqs, is_target=is_t.astype(np.uint8), depth=depth)
+                # NNG:416 binds (never with the reference's default 2**32): an order-dependent rule, carried out on the device by
+                # isocon_nn_graph itself; with several ranks every rank runs this call on its own (local, replicated)
+                best, row_ptr, cols, stats = st.nn_graph(is_target=is_t.astype(np.uint8), depth=depth)
+            else:
+                best, row_ptr, cols, stats = _graph(st, seqs, is_target=is_t.astype(np.uint8), depth=depth)
         finally:
             st.close()
         rec.add(edges=int(len(cols)), **{k: v for k, v in stats.items()})
