@@ -239,6 +239,7 @@ extern "C" int isocon_msa_build_ops_batch(isocon_store *s, uint32_t n_parts, con
     std::vector<uint32_t> part_of_row(n_rows), Lm(n_parts), slot_base((size_t)n_parts + 1, 0);
     for (uint32_t p = 0; p < n_parts; ++p) {
         if (first_row[p + 1] <= first_row[p]) { g_last_error = "a partition without rows"; return ISOCON_E_ARG; }
+        if (first_row[p + 1] > n_rows) { g_last_error = "a partition ends behind the last row"; return ISOCON_E_ARG; }          // (part_of_row has n_rows entries)
         for (uint32_t r = first_row[p]; r < first_row[p + 1]; ++r) {
             if (row_ids[r] >= n) { g_last_error = "row id out of range"; return ISOCON_E_ARG; }
             if (ops_ptr[r + 1] < ops_ptr[r]) return ISOCON_E_ARG;

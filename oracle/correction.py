@@ -14,11 +14,9 @@ import numpy as np
 _SYMS = np.frombuffer(b"ACGT-", dtype=np.uint8)
 
 
-def correct_rows(M, deg):
-    """M: uint8 [nr, ncols] of 'A','C','G','T','-'; deg: multiplicity per row.
-    Returns (packed bytes uint8, offsets int64[nr+1], n_cand int32[nr]) like isocon_msa_correct."""
-    M = np.ascontiguousarray(M)
-    deg = np.asarray(deg, dtype=np.int64)
+def _column_stats(M, deg):
+    """counts int64[5, ncols] (order A C G T -), majority index and count per column, the unambiguous columns, and the
+    partition's totals of the three error classes (insertions, deletions, substitutions) over them."""
     nr, ncols = M.shape
     sym_index = np.full(256, -1, dtype=np.int64)
     sym_index[_SYMS] = np.arange(5)
@@ -29,13 +27,36 @@ def correct_rows(M, deg):
     maj_idx = counts.argmax(axis=0)                                # first maximum in that order (max() over the dict)
     maj_cnt = counts.max(axis=0)
     unambiguous = (counts == maj_cnt[None, :]).sum(axis=0) == 1
-    maj_chr = _SYMS[maj_idx]
     maj_is_gap = maj_idx == 4
     tot = counts.sum(axis=0)
     c_ins = int((tot - maj_cnt)[unambiguous & maj_is_gap].sum())
     col_ok = unambiguous & ~maj_is_gap
     c_del = int(counts[4][col_ok].sum())
     c_subs = int((tot - maj_cnt - counts[4])[col_ok].sum())
+    return sym_index, counts, maj_idx, unambiguous, (c_ins, c_del, c_subs)
+
+
+def class_totals(M, deg):
+    """(c_ins, c_del, c_subs): the denominators of correct_rows' frequencies before their clamp to 1 -- what
+    isocon_msa_correct writes to out_class_totals."""
+    return _column_stats(np.ascontiguousarray(M), np.asarray(deg, dtype=np.int64))[4]
+
+
+def column_majority(M, deg):
+    """(majority symbol uint8[ncols], unambiguous bool[ncols]) of correct_rows' columns."""
+    _, _, maj_idx, unambiguous, _ = _column_stats(np.ascontiguousarray(M), np.asarray(deg, dtype=np.int64))
+    return _SYMS[maj_idx], unambiguous
+
+
+def correct_rows(M, deg):
+    """M: uint8 [nr, ncols] of 'A','C','G','T','-'; deg: multiplicity per row.
+    Returns (packed bytes uint8, offsets int64[nr+1], n_cand int32[nr]) like isocon_msa_correct."""
+    M = np.ascontiguousarray(M)
+    deg = np.asarray(deg, dtype=np.int64)
+    nr, ncols = M.shape
+    sym_index, counts, maj_idx, unambiguous, (c_ins, c_del, c_subs) = _column_stats(M, deg)
+    maj_chr = _SYMS[maj_idx]
+    maj_is_gap = maj_idx == 4
 
     # Per read: the unambiguous columns where it differs from the majority are its correctable positions; ceil(half) of
     # them are corrected, rarest first (frequency of the read's character in the column relative to the partition's
