@@ -353,6 +353,19 @@ int isocon_hw_pairs(isocon_store *s, const uint32_t *q, const uint32_t *t, const
                     int32_t *out, float *kernel_ms);
 
 /*
+ * isocon_hw_pairs without the limit of 512 diagonals: the same arguments, checks and (n_pairs, 5) output, for any k[p] <= 2^20 --
+ * edlib_traceback (modules/end_invariant_functions.py:593-620) with k >= 256, and get_all_NN (:661, :668: k = 10 + ignore_ends_len over
+ * a length window of 10 + 2 ignore_ends_len) with ignore_ends_len >= 121.  Every pair is classed on the host from the two lengths and
+ * k[p]: the pairs isocon_hw_pairs accepts go through it as one sub-list (their rows are the rows it returns; a call without any other
+ * pair IS that call), the others through un-banded kernels (one wavefront per pair, the whole query in 64-row blocks).  The vectors
+ * the path walk needs are kept per launch in at most 1 GiB of scratch: the wide pairs are cut into as many launches as that takes, and
+ * a single pair that needs more on its own is refused with ISOCON_E_UNSUPPORTED (isocon_last_error states its sizes).  So is a query of
+ * more than 4 096 bases against a target of more than 655 360.  *kernel_ms sums both parts.
+ */
+int isocon_hw_pairs_wide(isocon_store *s, const uint32_t *q, const uint32_t *t, const int32_t *k, uint64_t n_pairs,
+                         int32_t *out, float *kernel_ms);
+
+/*
  * Greedy partition of the nearest-neighbour graph into consensus centres and their members, on integer ids: what
  * get_partitions_no_copy (modules/partitions.py:301-413, called by partition_strings :416-593 on nx.reverse(G_star)) and
  * partition_highest_reachable_with_edge_degrees (modules/end_invariant_functions.py:405-533; nbr_tiebreak = 0) compute on networkx

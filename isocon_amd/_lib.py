@@ -96,6 +96,7 @@ SYMBOLS = {
     "isocon_msa_correct": (ctypes.c_int, [u8p, ctypes.c_uint32, ctypes.c_uint32, i32p, u8p, ctypes.c_uint64, u64p, i32p,
                                           ctypes.POINTER(ctypes.c_int64), f32p]),
     "isocon_hw_pairs": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, i32p, ctypes.c_uint64, i32p, f32p]),
+    "isocon_hw_pairs_wide": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, i32p, ctypes.c_uint64, i32p, f32p]),
 }
 
 _lib = None

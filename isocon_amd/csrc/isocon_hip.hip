@@ -27,6 +27,7 @@
 #include "msa_batch.hpp"
 #include "hw.hpp"
 #include "hw_tiles.hpp"
+#include "hw_full.hpp"
 #include "ed_lanes.hpp"
 #include "ed_bytes.hpp"
 #include "nn2_depth.hpp"
@@ -1017,6 +1018,7 @@ extern "C" int isocon_block_bound_pairs(isocon_store *s, const uint32_t *owner, 
 #include "sg_host.inc"
 #include "msa_host.inc"
 #include "hw_host.inc"
+#include "hw_full_host.inc"
 
 extern "C" int isocon_partition_ids(uint32_t n, const int32_t *degree, uint64_t n_edges, const uint32_t *edge_a, const uint32_t *edge_b,
                                     const uint32_t *rank, int32_t nbr_tiebreak, uint32_t *out_centre, int64_t *out_weight,

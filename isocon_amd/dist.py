@@ -423,11 +423,11 @@ def sharded_ed_pairs(store, a, b, k=None, dist=None, device=None):
     return out
 
 
-def sharded_hw_pairs(store, q, t, k, dist=None, device=None):
+def sharded_hw_pairs(store, q, t, k, dist=None, device=None, wide=False):
     """Infix alignments (SeqStore.hw_pairs: distance, start, end, leading / trailing insertion run) of the pairs (q[i] inside
     t[i]) computed by all ranks, gathered everywhere -- the candidate-vs-candidate graph of the statistical test
     (end_invariant_functions.get_all_NN) is an explicit pair list like the others; the reference's counterpart is the Pool
-    of end_invariant_functions.py:708-741."""
+    of end_invariant_functions.py:708-741.  wide: passed on to SeqStore.hw_pairs (bands above 512 diagonals)."""
     import torch
     if dist is None:
         import torch.distributed as dist  # noqa: PLC0415
@@ -441,7 +441,7 @@ def sharded_hw_pairs(store, q, t, k, dist=None, device=None):
         raise RuntimeError("sharded_hw_pairs: the ranks hold different pair lists / sequence sets")
     shards = _pair_shards(lens[q], lens[t], world)
     mine = shards[rank]
-    res = np.asarray(store.hw_pairs(q[mine], t[mine], kk[mine]), dtype=np.int32).reshape(-1) if len(mine) else np.zeros(0, np.int32)
+    res = np.asarray(store.hw_pairs(q[mine], t[mine], kk[mine], wide=wide), dtype=np.int32).reshape(-1) if len(mine) else np.zeros(0, np.int32)
     parts = _all_gather_ragged(dist, res, device)
     out = np.empty((len(q), 5), dtype=np.int32)
     for r in range(world):

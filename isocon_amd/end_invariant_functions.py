@@ -188,7 +188,9 @@ def edlib_traceback(x, y, mode="HW", task="path", k=1, end_threshold=0):
     """end_invariant_functions.py:593-620 for one pair (x = query, y = target)."""
     if mode != "HW" or task != "path":
         raise NotImplementedError("end_invariant_functions.edlib_traceback: only mode='HW', task='path' (the reference's only use, :661,:668)")
-    res = SeqStore([x, y]).hw_pairs([0], [1], [int(k)])
+    # (the banded kernels take up to 512 diagonals; beyond that the un-banded ones)
+    wide = 2 * int(k) + 1 + max(len(y) - len(x), 0) > 512
+    res = SeqStore([x, y]).hw_pairs([0], [1], [int(k)], wide=wide)
     return int(_ends_adjusted(res, [len(y)], end_threshold)[0])
 
 
@@ -259,11 +261,13 @@ def get_all_NN(batch_of_queries, global_index_in_matrix, start_index, seq_to_acc
         return all_neighbors_graph
     from .nearest_neighbor_graph import _process_group
     group = _process_group()            # one process per GPU: every rank aligns its share of the pairs, all get all results
+    # the widest band a pair of the window can need: up to 512 diagonals every pair takes the banded kernels (ignore_ends_len <= 120)
+    wide = window + 2 * max_ed_allowed + 1 > 512
     if group is None:
-        res = SeqStore(seqs).hw_pairs(q, t, np.full(len(q), max_ed_allowed, dtype=np.int32), reuse_buffer=True)       # (digested right below)
+        res = SeqStore(seqs).hw_pairs(q, t, np.full(len(q), max_ed_allowed, dtype=np.int32), reuse_buffer=True, wide=wide)       # (digested right below)
     else:
         from .dist import sharded_hw_pairs
-        res = sharded_hw_pairs(SeqStore(seqs), q, t, max_ed_allowed, dist=group)
+        res = sharded_hw_pairs(SeqStore(seqs), q, t, max_ed_allowed, dist=group, wide=wide)
     ed = _ends_adjusted(res, lens[t], ignore_ends_threshold)
     for p in np.flatnonzero((ed >= 0) & (ed <= max_variants)).tolist():
         all_neighbors_graph[accs[q[p]]][accs[t[p]]] = int(ed[p])

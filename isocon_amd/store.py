@@ -149,10 +149,11 @@ class SeqStore(object):
             _lib.check(rc, "isocon_qgram_bound_matrix")
             return row_ptr, out[:int(row_ptr[-1])]
 
-    def hw_pairs(self, q, t, k, return_ms=False, reuse_buffer=False):
+    def hw_pairs(self, q, t, k, return_ms=False, reuse_buffer=False, wide=False):
         """Infix (edlib "HW", task="path") alignment of sequence q[p] inside sequence t[p] with threshold k[p]:
         int32 [n, 5] = distance (-1 if > k), start, end, leading insertion run, trailing insertion run
-        (isocon_hw_pairs; reference call site end_invariant_functions.py:594)."""
+        (isocon_hw_pairs; reference call site end_invariant_functions.py:594).  wide: isocon_hw_pairs_wide -- pairs whose band
+        max(len_t - len_q, 0) + 2 k + 1 exceeds 512 diagonals are aligned too (un-banded kernels) instead of refused."""
         q = np.ascontiguousarray(q, dtype=np.uint32)
         t = np.ascontiguousarray(t, dtype=np.uint32)
         kk = np.ascontiguousarray(np.broadcast_to(np.asarray(k, dtype=np.int32), q.shape))
@@ -165,6 +166,10 @@ class SeqStore(object):
         else:
             out = np.empty((len(q), 5), dtype=np.int32)
         ms = ctypes.c_float(0)
+        if wide:
+            _lib.check(self._L.isocon_hw_pairs_wide(self._h, _ptr(q, _lib.u32p), _ptr(t, _lib.u32p), _ptr(kk, _lib.i32p), len(q),
+                                                    _ptr(out, _lib.i32p), ctypes.byref(ms)), "isocon_hw_pairs_wide")
+            return (out, ms.value) if return_ms else out
         _lib.check(self._L.isocon_hw_pairs(self._h, _ptr(q, _lib.u32p), _ptr(t, _lib.u32p), _ptr(kk, _lib.i32p), len(q),
                                            _ptr(out, _lib.i32p), ctypes.byref(ms)), "isocon_hw_pairs")
         return (out, ms.value) if return_ms else out
