@@ -366,6 +366,46 @@ int isocon_hw_pairs_wide(isocon_store *s, const uint32_t *q, const uint32_t *t, 
                          int32_t *out, float *kernel_ms);
 
 /*
+ * Device read tables of the hypothesis test: which reads support a candidate against its reference, and every read's error counts,
+ * from the stored read alignments -- the per-read loops of get_support (modules/functions.py:149-201), get_read_errors (:204-216) and
+ * read_errors_from_alignment (:495-522) as arrange_alignments_new_no_realign calls them per edge (modules/hypothesis_test_module.py:92-171).
+ * Integers and bit sets only: the probabilities and the p-value stay on the host.
+ *
+ * A table set holds the alignments of the reads of many candidates.  Row r is the pair of gapped rows (candidate's, read's)
+ * ref_rows / read_rows[row_ptr[r] .. row_ptr[r + 1]) (one row_ptr: both rows of an alignment are equally long), table k = rows
+ * first_row[k] .. first_row[k + 1] = the reads of one candidate (first_row[0] = 0, first_row[n_tables] = n_rows).
+ *   isocon_readtab_create        uploads the rows, builds the tables (k_rt_build) and returns out_errors[3 r ..] = (insertions, deletions,
+ *                                substitutions) of row r between the end gaps of either row == read_errors_from_alignment.
+ *                                ISOCON_E_ARG: a byte outside ACGT-, offsets that descend, rows of one table with different numbers of
+ *                                candidate bases.  The handle keeps, per row and 64-column block, the mask of columns without a
+ *                                candidate base, the mask of differing columns and the count of candidate bases before the block, and
+ *                                the reads' bytes; the candidates' bytes are not kept.
+ *   isocon_readtab_support       query q = one side of one edge: table q_table[q], kind q_kind[q], its variants var_ptr[q] .. var_ptr[q + 1]
+ *                                in the dict order of get_variant_coordinates (:89-146): var_pos = coordinate i on the candidate, var_u
+ *                                = u_v, var_type = the type letter ('I', 'D', 'S').  Bit j of out_bits[bits_ptr[q] + j / 64] = row j of
+ *                                the table passes every variant; out_count[q] = their number; the caller sizes the bit set
+ *                                (bits_ptr[q + 1] - bits_ptr[q] >= ceil(rows / 64), bits_ptr[0] = 0; spare words come back 0).
+ *                                  kind 0 (reads of c): pos = column of candidate base i of the row; passes iff no column of
+ *                                    [pos - 1, pos + u_v] inside the row differs between the two rows (:186-190).
+ *                                  kind 1 (reads of t): (before, after) = (2, u_v) for 'I', else (1, u_v + 1); passes iff
+ *                                    read_row[max(0, pos - before) .. min(len, pos + after)) equals the variant's snippet
+ *                                    snip_bytes[snip_ptr[v] .. snip_ptr[v + 1]) (v = index into the variant arrays), length included
+ *                                    (:192-199).  snip_ptr / snip_bytes may be NULL when no query of kind 1 has a variant.
+ *                                i in [-ref_len, 0) counts from the end as a Python index does; any other i outside [0, ref_len) is
+ *                                ISOCON_E_ARG (the per-read statement raises IndexError) unless the table has no rows.  u_v and the
+ *                                snippet length are not limited by the block size.
+ *   isocon_readtab_device_bytes  device memory the handle holds.
+ */
+typedef struct isocon_readtab isocon_readtab;
+int isocon_readtab_create(const uint8_t *ref_rows, const uint8_t *read_rows, const uint64_t *row_ptr, uint32_t n_rows, const uint32_t *first_row,
+                          uint32_t n_tables, isocon_readtab **out, uint32_t *out_errors, float *kernel_ms);
+int isocon_readtab_support(isocon_readtab *h, uint32_t n_queries, const uint32_t *q_table, const uint8_t *q_kind, const uint64_t *var_ptr,
+                           const int32_t *var_pos, const int32_t *var_u, const uint8_t *var_type, const uint64_t *snip_ptr, const uint8_t *snip_bytes,
+                           const uint64_t *bits_ptr, uint64_t *out_bits, uint32_t *out_count, float *kernel_ms);
+void isocon_readtab_destroy(isocon_readtab *h);
+uint64_t isocon_readtab_device_bytes(const isocon_readtab *h);
+
+/*
  * Greedy partition of the nearest-neighbour graph into consensus centres and their members, on integer ids: what
  * get_partitions_no_copy (modules/partitions.py:301-413, called by partition_strings :416-593 on nx.reverse(G_star)) and
  * partition_highest_reachable_with_edge_degrees (modules/end_invariant_functions.py:405-533; nbr_tiebreak = 0) compute on networkx

@@ -31,6 +31,7 @@
 #include "ed_lanes.hpp"
 #include "ed_bytes.hpp"
 #include "nn2_depth.hpp"
+#include "readtab.hpp"
 
 namespace isocon {
 thread_local std::string g_last_error;
@@ -133,6 +134,7 @@ enum {
     SLOT_MSA_IN, SLOT_MSA_OUT, SLOT_MSA_DEG, SLOT_MSA_COUNTS, SLOT_MSA_MAJ, SLOT_MSA_FLAGS, SLOT_MSA_TOT, SLOT_MSA_NCAND, SLOT_MSA_LEN, SLOT_MSA_OFF, SLOT_MSA_PACKED, SLOT_MSA_ROWS, SLOT_MSA_OPS, SLOT_MSA_OPTR, SLOT_MSA_LONGEST, SLOT_MSA_WIDTH, SLOT_MSA_CSLOT, SLOT_MSA_LTOT, SLOT_MSA_WIDE, SLOT_MSA_PROW, SLOT_MSA_PCOL, SLOT_MSA_PPTR, SLOT_MSA_PBYTES, SLOT_MSAB_PART, SLOT_MSAB_FIRST, SLOT_MSAB_LM, SLOT_MSAB_SBASE, SLOT_MSAB_NCOLS, SLOT_MSAB_MOFF, SLOT_MSAB_CBASE, SLOT_MSAB_CBP, SLOT_MSAB_CBC, SLOT_MSAB_CBR,
     SLOT_HW_Q, SLOT_HW_T, SLOT_HW_K, SLOT_HW_OUT, SLOT_HW_TRACE, SLOT_HW_CTR, SLOT_HW_TILEQ, SLOT_HW_LANES, SLOT_HW_PQ, SLOT_HW_KEY, SLOT_HW_HIST, SLOT_HW_CURSOR, SLOT_HW_TBASE, SLOT_HW_CLS,
     SLOT_PACK_ASCII, SLOT_PACK_OFF, SLOT_PACK_BAD, SLOT_PACK_HIST, SLOT_PACK_FLAGS, SLOT_EB_A, SLOT_EB_B, SLOT_EB_K, SLOT_EB_OUT, SLOT_EB_ROWS, SLOT_SCAN_TMP, SLOT_SCAN_SUMS,
+    SLOT_RT_REF, SLOT_RT_IN, SLOT_RT_OUT,
     SLOT_COUNT
 };
 static_assert(SLOT_COUNT <= 160, "ScratchPool::slots too small");
@@ -1019,6 +1021,7 @@ extern "C" int isocon_block_bound_pairs(isocon_store *s, const uint32_t *owner, 
 #include "msa_host.inc"
 #include "hw_host.inc"
 #include "hw_full_host.inc"
+#include "readtab_host.inc"
 
 extern "C" int isocon_partition_ids(uint32_t n, const int32_t *degree, uint64_t n_edges, const uint32_t *edge_a, const uint32_t *edge_b,
                                     const uint32_t *rank, int32_t nbr_tiebreak, uint32_t *out_centre, int64_t *out_weight,

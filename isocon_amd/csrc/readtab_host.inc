@@ -1,0 +1,195 @@
+// readtab_host.inc -- host side of the device read tables of the statistical test (included by isocon_hip.hip): isocon_readtab_create /
+// _support / _destroy / _device_bytes.  The tables live in the handle; the candidates' rows (needed by the build only), the queries and
+// the answers pass through slots of the process' scratch pool.
+
+struct isocon_readtab {
+    uint64_t *d_row_ptr = nullptr, *d_blk_ptr = nullptr, *d_nob = nullptr, *d_diff = nullptr;
+    uint32_t *d_pre = nullptr, *d_first = nullptr;
+    uint8_t *d_read = nullptr;
+    uint32_t n_rows = 0, n_tables = 0;
+    std::vector<uint32_t> first_row;          // host copies: what a query is checked against
+    std::vector<int64_t> ref_len;             // candidate bases of every row of table k (-1: the table has no rows)
+    uint64_t device_bytes = 0;
+};
+
+namespace {
+
+template <class T>
+int rt_alloc(isocon_readtab *h, T **p, size_t count)
+{
+    const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
+    if (hipMalloc((void **)p, bytes) != hipSuccess) { *p = nullptr; (void)hipGetLastError(); g_last_error = "hipMalloc(read tables, " + std::to_string(bytes) + " B) failed"; return ISOCON_E_HIP; }
+    h->device_bytes += bytes;
+    return ISOCON_OK;
+}
+
+// appends n items to a byte image at the next multiple of 8 and returns their offset
+template <class T>
+size_t rt_pack(std::vector<uint8_t> &img, const T *src, size_t n)
+{
+    const size_t at = (img.size() + 7) & ~(size_t)7;
+    img.resize(at + n * sizeof(T));
+    if (n) memcpy(img.data() + at, src, n * sizeof(T));
+    return at;
+}
+
+int readtab_create_impl(isocon_readtab *h, const uint8_t *ref_rows, const uint8_t *read_rows, const uint64_t *row_ptr, uint32_t n_rows, const uint32_t *first_row,
+                        uint32_t n_tables, uint32_t *out_errors, float *kernel_ms)
+{
+    std::vector<uint64_t> blk_ptr((size_t)n_rows + 1, 0);
+    for (uint32_t r = 0; r < n_rows; ++r) blk_ptr[r + 1] = blk_ptr[r] + (row_ptr[r + 1] - row_ptr[r] + 63) / 64;
+    const uint64_t base = row_ptr[0], total = row_ptr[n_rows] - base, n_blk = blk_ptr[n_rows];
+    std::vector<uint64_t> rel((size_t)n_rows + 1);
+    for (uint32_t r = 0; r <= n_rows; ++r) rel[r] = row_ptr[r] - base;
+    h->n_rows = n_rows;
+    h->n_tables = n_tables;
+    h->first_row.assign(first_row, first_row + n_tables + 1);
+    int rc;
+    if ((rc = rt_alloc(h, &h->d_row_ptr, (size_t)n_rows + 1)) || (rc = rt_alloc(h, &h->d_blk_ptr, (size_t)n_rows + 1)) || (rc = rt_alloc(h, &h->d_nob, n_blk)) ||
+        (rc = rt_alloc(h, &h->d_diff, n_blk)) || (rc = rt_alloc(h, &h->d_pre, n_blk)) || (rc = rt_alloc(h, &h->d_first, (size_t)n_tables + 1)) ||
+        (rc = rt_alloc(h, &h->d_read, total)))
+        return rc;
+    DevBuf d_ref(&g_scratch, SLOT_RT_REF), d_out(&g_scratch, SLOT_RT_OUT);
+    if ((rc = d_ref.alloc(total)) || (rc = d_out.alloc(((size_t)n_rows * 4 + 1) * 4))) return rc;
+    ISO_HIP_CHECK(copy_h2d(h->d_row_ptr, rel.data(), ((size_t)n_rows + 1) * 8));
+    ISO_HIP_CHECK(copy_h2d(h->d_blk_ptr, blk_ptr.data(), ((size_t)n_rows + 1) * 8));
+    ISO_HIP_CHECK(copy_h2d(h->d_first, first_row, ((size_t)n_tables + 1) * 4));
+    if (total) {
+        ISO_HIP_CHECK(copy_h2d(d_ref.p, ref_rows + base, total));
+        ISO_HIP_CHECK(copy_h2d(h->d_read, read_rows + base, total));
+    }
+    uint32_t *d_bad = d_out.as<uint32_t>() + (size_t)n_rows * 4;
+    ISO_HIP_CHECK(hipMemset(d_bad, 0, 4));
+    EventTimer tm;
+    if (n_rows) {
+        tm.start();
+        hipLaunchKernelGGL(k_rt_build, dim3((n_rows + 3) / 4), dim3(256), 0, 0, d_ref.as<uint8_t>(), h->d_read, h->d_row_ptr, h->d_blk_ptr, n_rows, h->d_nob, h->d_diff,
+                           h->d_pre, d_out.as<uint32_t>(), d_bad);
+        ISO_HIP_CHECK(hipGetLastError());
+        tm.stop();
+    }
+    if (kernel_ms) *kernel_ms = tm.total;
+    std::vector<uint32_t> res((size_t)n_rows * 4 + 1);
+    ISO_HIP_CHECK(copy_d2h(res.data(), d_out.p, res.size() * 4));
+    if (res[(size_t)n_rows * 4]) { g_last_error = "isocon_readtab_create: a row holds a byte outside ACGT-"; return ISOCON_E_ARG; }
+    h->ref_len.assign(n_tables, -1);
+    for (uint32_t k = 0; k < n_tables; ++k)
+        for (uint32_t r = first_row[k]; r < first_row[k + 1]; ++r) {
+            const int64_t bases = res[(size_t)r * 4 + 3];
+            if (h->ref_len[k] < 0) h->ref_len[k] = bases;
+            else if (h->ref_len[k] != bases) {
+                g_last_error = "isocon_readtab_create: the rows of table " + std::to_string(k) + " hold " + std::to_string(h->ref_len[k]) + " and " + std::to_string(bases) +
+                               " candidate bases";
+                return ISOCON_E_ARG;
+            }
+        }
+    for (uint32_t r = 0; r < n_rows; ++r)
+        for (int e = 0; e < 3; ++e) out_errors[(size_t)r * 3 + e] = res[(size_t)r * 4 + e];
+    return ISOCON_OK;
+}
+
+}  // namespace
+
+extern "C" void isocon_readtab_destroy(isocon_readtab *h)
+{
+    if (!h) return;
+    void *bufs[] = {h->d_row_ptr, h->d_blk_ptr, h->d_nob, h->d_diff, h->d_pre, h->d_first, h->d_read};
+    for (void *p : bufs) if (p) (void)hipFree(p);
+    delete h;
+}
+
+extern "C" uint64_t isocon_readtab_device_bytes(const isocon_readtab *h) { return h ? h->device_bytes : 0; }
+
+extern "C" int isocon_readtab_create(const uint8_t *ref_rows, const uint8_t *read_rows, const uint64_t *row_ptr, uint32_t n_rows, const uint32_t *first_row,
+                                     uint32_t n_tables, isocon_readtab **out, uint32_t *out_errors, float *kernel_ms)
+{
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (!out) return ISOCON_E_ARG;
+    *out = nullptr;
+    if (!row_ptr || !first_row || (n_rows && !out_errors)) return ISOCON_E_ARG;
+    if (first_row[0] != 0 || first_row[n_tables] != n_rows) { g_last_error = "isocon_readtab_create: first_row does not span the rows"; return ISOCON_E_ARG; }
+    for (uint32_t k = 0; k < n_tables; ++k)
+        if (first_row[k + 1] < first_row[k]) { g_last_error = "isocon_readtab_create: first_row descends"; return ISOCON_E_ARG; }
+    for (uint32_t r = 0; r < n_rows; ++r)
+        if (row_ptr[r + 1] < row_ptr[r] || row_ptr[r + 1] - row_ptr[r] > 0x7ffffff0ull) { g_last_error = "isocon_readtab_create: bad row_ptr at row " + std::to_string(r); return ISOCON_E_ARG; }
+    if (row_ptr[n_rows] > row_ptr[0] && (!ref_rows || !read_rows)) return ISOCON_E_ARG;
+    isocon_readtab *h = new isocon_readtab();
+    const int rc = readtab_create_impl(h, ref_rows, read_rows, row_ptr, n_rows, first_row, n_tables, out_errors, kernel_ms);
+    if (rc) { isocon_readtab_destroy(h); (void)hipGetLastError(); return rc; }
+    *out = h;
+    return ISOCON_OK;
+}
+
+extern "C" int isocon_readtab_support(isocon_readtab *h, uint32_t n_queries, const uint32_t *q_table, const uint8_t *q_kind, const uint64_t *var_ptr,
+                                      const int32_t *var_pos, const int32_t *var_u, const uint8_t *var_type, const uint64_t *snip_ptr, const uint8_t *snip_bytes,
+                                      const uint64_t *bits_ptr, uint64_t *out_bits, uint32_t *out_count, float *kernel_ms)
+{
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (!h) return ISOCON_E_ARG;
+    if (!n_queries) return ISOCON_OK;
+    if (!q_table || !q_kind || !var_ptr || !bits_ptr || !out_count) return ISOCON_E_ARG;
+    const uint64_t n_var = var_ptr[n_queries], n_words = bits_ptr[n_queries];
+    if (n_var > ((uint64_t)1 << 40) || n_words > ((uint64_t)1 << 40)) return ISOCON_E_ARG;
+    if (var_ptr[0] != 0 || bits_ptr[0] != 0 || (n_var && (!var_pos || !var_u || !var_type)) || (n_words && !out_bits)) return ISOCON_E_ARG;
+    bool any_snippet = false;
+    std::vector<uint32_t> pos((size_t)n_var);
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        if (q_table[q] >= h->n_tables || q_kind[q] > 1 || var_ptr[q + 1] < var_ptr[q] || var_ptr[q + 1] > n_var || bits_ptr[q + 1] < bits_ptr[q] || bits_ptr[q + 1] > n_words) {
+            g_last_error = "isocon_readtab_support: bad table, kind or offsets in query " + std::to_string(q);
+            return ISOCON_E_ARG;
+        }
+        const uint32_t k = q_table[q], nr = h->first_row[k + 1] - h->first_row[k];
+        if (bits_ptr[q + 1] - bits_ptr[q] < ((uint64_t)nr + 63) / 64) { g_last_error = "isocon_readtab_support: the bit set of query " + std::to_string(q) + " is too small"; return ISOCON_E_ARG; }
+        const int64_t ref_len = h->ref_len[k];
+        for (uint64_t v = var_ptr[q]; v < var_ptr[q + 1]; ++v) {
+            int64_t i = var_pos[v];
+            if (ref_len < 0) { pos[v] = 0; continue; }          // no rows: nothing is indexed
+            if (i < -ref_len || i >= ref_len) {          // the per-read statement raises IndexError here
+                g_last_error = "isocon_readtab_support: coordinate " + std::to_string(i) + " of query " + std::to_string(q) + " outside a candidate of " + std::to_string(ref_len) + " bases";
+                return ISOCON_E_ARG;
+            }
+            pos[v] = (uint32_t)(i < 0 ? i + ref_len : i);
+        }
+        any_snippet |= q_kind[q] == 1 && var_ptr[q + 1] > var_ptr[q];
+    }
+    std::vector<uint64_t> no_snippets;
+    if (any_snippet) {
+        if (!snip_ptr) return ISOCON_E_ARG;
+        for (uint64_t v = 0; v < n_var; ++v)
+            if (snip_ptr[v + 1] < snip_ptr[v]) { g_last_error = "isocon_readtab_support: snip_ptr descends"; return ISOCON_E_ARG; }
+        if (snip_ptr[n_var] > snip_ptr[0] && !snip_bytes) return ISOCON_E_ARG;
+    } else {
+        no_snippets.assign((size_t)n_var + 1, 0);
+        snip_ptr = no_snippets.data();
+    }
+    const uint64_t snip_base = snip_ptr[0], snip_total = snip_ptr[n_var] - snip_base;
+    std::vector<uint64_t> snip_rel((size_t)n_var + 1);
+    for (uint64_t v = 0; v <= n_var; ++v) snip_rel[v] = snip_ptr[v] - snip_base;
+    // one image of the queries, one copy
+    std::vector<uint8_t> img;
+    const size_t o_var_ptr = rt_pack(img, var_ptr, (size_t)n_queries + 1), o_snip_ptr = rt_pack(img, snip_rel.data(), snip_rel.size()),
+                 o_bits_ptr = rt_pack(img, bits_ptr, (size_t)n_queries + 1), o_table = rt_pack(img, q_table, n_queries), o_pos = rt_pack(img, pos.data(), pos.size()),
+                 o_u = rt_pack(img, var_u, (size_t)n_var), o_kind = rt_pack(img, q_kind, n_queries), o_type = rt_pack(img, var_type, (size_t)n_var),
+                 o_snip = rt_pack(img, snip_total ? snip_bytes + snip_base : nullptr, (size_t)snip_total);
+    DevBuf d_in(&g_scratch, SLOT_RT_IN), d_out(&g_scratch, SLOT_RT_OUT);
+    const size_t out_bytes = (size_t)n_words * 8 + (size_t)n_queries * 4;
+    int rc;
+    if ((rc = d_in.alloc(img.size())) || (rc = d_out.alloc(out_bytes))) return rc;
+    ISO_HIP_CHECK(copy_h2d(d_in.p, img.data(), img.size()));
+    const uint8_t *in = d_in.as<uint8_t>();
+    RtTables T{h->d_row_ptr, h->d_blk_ptr, h->d_nob, h->d_diff, h->d_pre, h->d_read, h->d_first};
+    RtQueries Q{(const uint32_t *)(in + o_table), in + o_kind, (const uint64_t *)(in + o_var_ptr), (const uint32_t *)(in + o_pos), (const int32_t *)(in + o_u), in + o_type,
+                (const uint64_t *)(in + o_snip_ptr), in + o_snip, (const uint64_t *)(in + o_bits_ptr), n_queries};
+    if (n_words) ISO_HIP_CHECK(hipMemset(d_out.p, 0, (size_t)n_words * 8));          // (words beyond a table's rows)
+    EventTimer tm;
+    tm.start();
+    hipLaunchKernelGGL(k_rt_support, dim3((n_queries + 3) / 4), dim3(256), 0, 0, T, Q, d_out.as<uint64_t>(), (uint32_t *)(d_out.as<uint8_t>() + (size_t)n_words * 8));
+    ISO_HIP_CHECK(hipGetLastError());
+    tm.stop();
+    if (kernel_ms) *kernel_ms = tm.total;
+    std::vector<uint8_t> res(out_bytes);
+    ISO_HIP_CHECK(copy_d2h(res.data(), d_out.p, out_bytes));
+    if (n_words) memcpy(out_bits, res.data(), (size_t)n_words * 8);
+    memcpy(out_count, res.data() + (size_t)n_words * 8, (size_t)n_queries * 4);
+    return ISOCON_OK;
+}

@@ -14,11 +14,14 @@ bookkeeping on the host as in the reference.  With base qualities (a `ccs_dict`:
 come from the qualities (functions.get_read_ccs_probabilities_c / _t), computed on the same read tables."""
 from __future__ import annotations
 
+import ctypes
 import decimal
 import math
+import os
 
 import numpy as np
 
+from . import _lib
 from . import functions
 from . import SW_alignment_module as SWM
 
@@ -270,43 +273,254 @@ def _build_tables(items):
 
 
 _TABLES = {}        # id(read-alignment dict) -> (the dict, its alignment tuples, table); reset by clear_tables()
+_DEVICE_TABLES = {}     # the same for the tables kept on the device (_DeviceTable)
 
 
 def clear_tables():
     _TABLES.clear()
+    for tab in {id(hit[2].set): hit[2].set for hit in _DEVICE_TABLES.values()}.values():
+        tab.free()
+    _DEVICE_TABLES.clear()
 
 
-def _tables_for(wanted):
+def _tables_for(wanted, cache=None, build=None):
     """{id(read_alignments): table} for [(ref_seq, read_alignments)]; a table is rebuilt only when the candidate's reads or
-    their alignments have changed since the last round (the loop keeps most partitions untouched from round to round)."""
+    their alignments have changed since the last round (the loop keeps most partitions untouched from round to round).
+    cache / build: the host tables (_TABLES, _build_tables) unless given."""
+    cache = _TABLES if cache is None else cache
+    build = _build_tables if build is None else build
     out, todo = {}, []
     for ref_seq, ra in wanted:
         if id(ra) in out:
             continue
         stamp = list(ra.values())           # the alignment tuples themselves (kept alive: identities cannot be recycled)
-        hit = _TABLES.get(id(ra))
+        hit = cache.get(id(ra))
         if (hit is not None and hit[0] is ra and len(hit[1]) == len(stamp) and all(a is b for a, b in zip(hit[1], stamp))
                 and hit[2].ref_len == len(ref_seq)):
             out[id(ra)] = hit[2]
         else:
             out[id(ra)] = None
             todo.append((ref_seq, ra, stamp))
-    if len(_TABLES) > 200000:
-        _TABLES.clear()
+    if len(cache) > 200000:
+        cache.clear()          # (a device set goes with its last table)
     for lo in range(0, len(todo), 2048):                 # bounded batches: the shared arrays stay small
         part = todo[lo:lo + 2048]
-        for (ref_seq, ra, stamp), tab in zip(part, _build_tables([(len(r), a) for r, a, _ in part])):
-            _TABLES[id(ra)] = (ra, stamp, tab)
+        for (ref_seq, ra, stamp), tab in zip(part, build([(len(r), a) for r, a, _ in part])):
+            cache[id(ra)] = (ra, stamp, tab)
             out[id(ra)] = tab
     return out
 
 
+# ---- the read tables on the device (isocon_readtab_*: csrc/readtab.hpp) ----
+# The integer work of a test -- the column of a candidate position in every read's alignment, the window comparisons, the error
+# counts -- for all edges of a round in one call per table set; the probabilities and the bound stay on the host (_test_on_supporters).
+DEVICE_STATS = {"create_calls": 0, "rows_uploaded": 0, "support_calls": 0, "queries": 0, "kernel_ms": 0.0}
+_HAS_DEVICE = None
+
+
+def _variant_listed(name):
+    """is `name` listed in ISOCON_DEBUG_VARIANT (name[=value],name,...)?"""
+    return any(item.split("=")[0] == name for item in os.environ.get("ISOCON_DEBUG_VARIANT", "").split(","))
+
+
+def device_tables_enabled():
+    """the tests of a round go through the device tables: a GPU is there and ISOCON_DEBUG_VARIANT=stat_host_tables is not set"""
+    global _HAS_DEVICE
+    if _variant_listed("stat_host_tables"):
+        return False
+    if _HAS_DEVICE is None:
+        _HAS_DEVICE = _lib.load().isocon_device_count() > 0
+    return _HAS_DEVICE
+
+
+def device_table_bytes():
+    """device memory held by the cached table sets"""
+    return sum(s.bytes for s in {id(hit[2].set): hit[2].set for hit in _DEVICE_TABLES.values()}.values())
+
+
+def _ptr(a, typ):
+    return a.ctypes.data_as(typ)
+
+
+class _DeviceSet(object):
+    """One isocon_readtab handle: the tables of up to 2048 candidates.  Freed by clear_tables(), or with its last table."""
+
+    def __init__(self, handle):
+        self.handle = handle
+        self.bytes = int(_lib.lib().isocon_readtab_device_bytes(handle))
+
+    def free(self):
+        if self.handle is not None:
+            _lib.lib().isocon_readtab_destroy(self.handle)
+            self.handle, self.bytes = None, 0
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:          # (interpreter shutdown)
+            pass
+
+
+class _DeviceTable(object):
+    """table k of a set: what _test_on_supporters needs on the host (sizes and error counts), the rest lives in the set"""
+    __slots__ = ("set", "k", "n", "ref_len", "ins", "dele", "sub")
+
+
+def _pack_rows(items):
+    """the rows of [(ref_len, read_alignments)] as isocon_readtab_create takes them: (candidate rows, read rows, row_ptr, first_row)"""
+    rows_ref, rows_read, first_row = [], [], [0]
+    for _, ra in items:
+        for v in ra.values():
+            if len(v[0]) != len(v[1]):
+                raise ValueError("the two rows of a read alignment differ in length")
+            rows_ref.append(v[0])
+            rows_read.append(v[1])
+        first_row.append(len(rows_ref))
+    n = len(rows_ref)
+    row_ptr = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum(np.fromiter((len(r) for r in rows_ref), dtype=np.uint64, count=n), out=row_ptr[1:])
+    ref = np.frombuffer("".join(rows_ref).encode("ascii"), dtype=np.uint8)
+    read = np.frombuffer("".join(rows_read).encode("ascii"), dtype=np.uint8)
+    return ref, read, row_ptr, np.asarray(first_row, dtype=np.uint32)
+
+
+def _build_device_tables(items):
+    """_DeviceTable objects for [(ref_len, read_alignments)]: one table set"""
+    L = _lib.lib()
+    ref, read, row_ptr, first_row = _pack_rows(items)
+    n = len(row_ptr) - 1
+    errors = np.zeros((max(n, 1), 3), dtype=np.uint32)
+    handle, ms = ctypes.c_void_p(), ctypes.c_float(0.0)
+    _lib.check(L.isocon_readtab_create(_ptr(ref, _lib.u8p), _ptr(read, _lib.u8p), _ptr(row_ptr, _lib.u64p), n, _ptr(first_row, _lib.u32p), len(items),
+                                       ctypes.byref(handle), _ptr(errors, _lib.u32p), ctypes.byref(ms)), "isocon_readtab_create")
+    DEVICE_STATS["create_calls"] += 1
+    DEVICE_STATS["rows_uploaded"] += n
+    DEVICE_STATS["kernel_ms"] += ms.value
+    dset = _DeviceSet(handle)
+    errors = errors[:n].astype(np.int64)
+    tables = []
+    for k, (ref_len, _) in enumerate(items):
+        r0, r1 = int(first_row[k]), int(first_row[k + 1])
+        t = _DeviceTable()
+        t.set, t.k, t.n, t.ref_len = dset, k, r1 - r0, ref_len
+        t.ins, t.dele, t.sub = errors[r0:r1, 0], errors[r0:r1, 1], errors[r0:r1, 2]
+        tables.append(t)
+    return tables
+
+
+def _pack_queries(queries):
+    """[(table index, kind, variant_coords, snippets or None, rows of the table)] as isocon_readtab_support takes them: (q_table,
+    q_kind, var_ptr, var_pos, var_u, var_type, snip_ptr, snip_bytes, bits_ptr)"""
+    q_table, q_kind, var_ptr, var_pos, var_u, var_type, snip_len, snips, bits_ptr = [], [], [0], [], [], [], [], [], [0]
+    for k, kind, coords, snippets, n_rows in queries:
+        q_table.append(k)
+        q_kind.append(kind)
+        for i, (v_type, _, u_v) in coords.items():
+            var_pos.append(i)
+            var_u.append(u_v)
+            var_type.append(ord(v_type))
+            text = snippets[i] if kind else ""
+            snips.append(text)
+            snip_len.append(len(text))
+        var_ptr.append(len(var_pos))
+        bits_ptr.append(bits_ptr[-1] + (n_rows + 63) // 64)
+    snip_ptr = np.zeros(len(snip_len) + 1, dtype=np.uint64)
+    np.cumsum(np.asarray(snip_len, dtype=np.uint64), out=snip_ptr[1:])
+    snip_bytes = np.frombuffer("".join(snips).encode("ascii"), dtype=np.uint8)
+    if len(snip_bytes) == 0:
+        snip_bytes = np.zeros(1, dtype=np.uint8)
+    return (np.asarray(q_table, dtype=np.uint32), np.asarray(q_kind, dtype=np.uint8), np.asarray(var_ptr, dtype=np.uint64),
+            np.asarray(var_pos, dtype=np.int32), np.asarray(var_u, dtype=np.int32), np.asarray(var_type, dtype=np.uint8), snip_ptr, snip_bytes,
+            np.asarray(bits_ptr, dtype=np.uint64))
+
+
+def _rows_of_bits(words, n_rows):
+    """indices of the set bits among the first n_rows of a bit set (uint64 words, bit j of word j // 64)"""
+    return np.flatnonzero(np.unpackbits(words.view(np.uint8), bitorder="little")[:n_rows])
+
+
+def _device_support(handle, queries):
+    """one isocon_readtab_support call: the supporting rows (ascending indices into its table) of every query of _pack_queries"""
+    if not queries:
+        return []
+    q_table, q_kind, var_ptr, var_pos, var_u, var_type, snip_ptr, snip_bytes, bits_ptr = _pack_queries(queries)
+    bits = np.zeros(max(int(bits_ptr[-1]), 1), dtype=np.uint64)
+    count = np.zeros(len(queries), dtype=np.uint32)
+    ms = ctypes.c_float(0.0)
+    _lib.check(_lib.lib().isocon_readtab_support(handle, len(queries), _ptr(q_table, _lib.u32p), _ptr(q_kind, _lib.u8p), _ptr(var_ptr, _lib.u64p),
+                                                 _ptr(var_pos, _lib.i32p), _ptr(var_u, _lib.i32p), _ptr(var_type, _lib.u8p), _ptr(snip_ptr, _lib.u64p),
+                                                 _ptr(snip_bytes, _lib.u8p), _ptr(bits_ptr, _lib.u64p), _ptr(bits, _lib.u64p), _ptr(count, _lib.u32p),
+                                                 ctypes.byref(ms)), "isocon_readtab_support")
+    DEVICE_STATS["support_calls"] += 1
+    DEVICE_STATS["queries"] += len(queries)
+    DEVICE_STATS["kernel_ms"] += ms.value
+    out = []
+    for q, (_, _, _, _, n_rows) in enumerate(queries):
+        sup = _rows_of_bits(bits[int(bits_ptr[q]):int(bits_ptr[q + 1])], n_rows) if count[q] else np.zeros(0, dtype=np.int64)
+        assert len(sup) == int(count[q])
+        out.append(sup)
+    return out
+
+
+def _in_range(coords, ref_len):
+    return all(-ref_len <= i < ref_len for i in coords)
+
+
+def _tests_on_device(live, of_edge, C, read_partition):
+    """{edge: (variant_coords_t, p_value, supporting reads, reads used)} for the edges of a round (no base qualities): supporters and
+    error counts from the device tables, one support call per table set.  An edge with a variant coordinate that the per-read
+    statement cannot index stays on the host tables, where it raises as it always did."""
+    prepared, on_host = {}, []
+    for e in live:
+        c_acc, t_acc = e
+        ev = _edge_variants(C[t_acc], C[c_acc], of_edge[e][0], of_edge[e][1])
+        if _in_range(ev[2], len(C[c_acc])) and _in_range(ev[1], len(C[t_acc])):
+            prepared[e] = ev
+        else:
+            on_host.append(e)
+    tables = _tables_for([(C[acc], read_partition[acc]) for e in prepared for acc in e], _DEVICE_TABLES, _build_device_tables)
+    by_set = {}          # id(set) -> (set, its queries, where each answer goes)
+    for e, ev in prepared.items():
+        tab_c, tab_t = tables[id(read_partition[e[0]])], tables[id(read_partition[e[1]])]
+        for side, tab, kind, coords, snippets in ((0, tab_c, 0, ev[2], None), (1, tab_t, 1, ev[1], ev[3])):
+            group = by_set.setdefault(id(tab.set), (tab.set, [], []))
+            group[1].append((tab.k, kind, coords, snippets, tab.n))
+            group[2].append((e, side))
+    supporters = {}
+    for dset, queries, where in by_set.values():
+        for key, sup in zip(where, _device_support(dset.handle, queries)):
+            supporters[key] = sup
+    results = {}
+    for e, ev in prepared.items():
+        variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c = ev
+        results[e] = _test_on_supporters(C[e[1]], variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c,
+                                         tables[id(read_partition[e[0]])], tables[id(read_partition[e[1]])], supporters[(e, 0)], supporters[(e, 1)])
+    if on_host:
+        host = _tables_for([(C[acc], read_partition[acc]) for e in on_host for acc in e])
+        for e in on_host:
+            results[e] = _test_on_tables(C[e[1]], C[e[0]], of_edge[e][0], of_edge[e][1], host[id(read_partition[e[0]])], host[id(read_partition[e[1]])])
+    return results
+
+
+def _edge_variants(t_seq, c_seq, alignment_tc, alignment_ct):
+    """(variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c) of an edge from its two alignments"""
+    aln_t, aln_c, variants = _candidate_vs_reference(alignment_tc, alignment_ct)
+    return (variants,) + tuple(functions.get_variant_coordinates(t_seq, c_seq, aln_t, aln_c, variants))
+
+
 def _test_on_tables(t_seq, c_seq, alignment_tc, alignment_ct, tab_c, tab_t, ccs_dict=None, max_phred_q_trusted=None):
     """_test_on_alignments on the read tables of c and t: same tuple, the supporting reads as a count."""
-    aln_t, aln_c, variants = _candidate_vs_reference(alignment_tc, alignment_ct)
-    variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c = functions.get_variant_coordinates(t_seq, c_seq, aln_t, aln_c, variants)
+    variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c = _edge_variants(t_seq, c_seq, alignment_tc, alignment_ct)
     sup_c = np.flatnonzero(tab_c.agree_with_candidate(variant_coords_c))
     sup_t = np.flatnonzero(tab_t.show_snippets(variant_coords_t, alignment_c_to_t))
+    return _test_on_supporters(t_seq, variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c, tab_c, tab_t, sup_c, sup_t,
+                               ccs_dict, max_phred_q_trusted)
+
+
+def _test_on_supporters(t_seq, variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c, tab_c, tab_t, sup_c, sup_t,
+                        ccs_dict=None, max_phred_q_trusted=None):
+    """The test of an edge once the supporting reads are known (sup_c / sup_t: ascending row indices into the tables of c / t, host
+    or device tables alike): error probabilities per read and the bound."""
     n_support = len(sup_c) + len(sup_t)
     if len(variants) == 0:
         return variant_coords_t, 0.0, n_support, tab_c.n + tab_t.n
@@ -402,7 +616,11 @@ def do_statistical_tests_per_edge(nearest_neighbor_graph, C, X, read_partition, 
     alignments = SWM._align_pairs(pairs, [-3] * len(pairs), 2, 3, 1) if pairs else []
     of_edge = {e: (alignments[2 * i], alignments[2 * i + 1]) for i, e in enumerate(live)}
     p_values = {c_acc: {} for c_acc in nearest_neighbor_graph}
-    tables = _tables_for([(C[acc], read_partition[acc]) for e in live for acc in e])
+    on_device = not ccs_dict and device_tables_enabled()
+    if on_device:
+        done = _tests_on_device(live, of_edge, C, read_partition)
+    else:
+        tables = _tables_for([(C[acc], read_partition[acc]) for e in live for acc in e])
     for c_acc, t_acc in edges:
         if (c_acc, t_acc) not in of_edge:
             p_values[c_acc][t_acc] = (1.0, 1.0, 0, 0, "")
@@ -412,8 +630,11 @@ def do_statistical_tests_per_edge(nearest_neighbor_graph, C, X, read_partition, 
         if ccs_dict:
             for x_acc in read_partition[c_acc]:
                 assert X[x_acc] == ccs_dict[x_acc].seq
-        delta_t, p_value, n_support, used = _test_on_tables(C[t_acc], C[c_acc], tc, ct, tables[id(read_partition[c_acc])],
-                                                            tables[id(read_partition[t_acc])], ccs_dict, getattr(params, "max_phred_q_trusted", None))
+        if on_device:
+            delta_t, p_value, n_support, used = done[(c_acc, t_acc)]
+        else:
+            delta_t, p_value, n_support, used = _test_on_tables(C[t_acc], C[c_acc], tc, ct, tables[id(read_partition[c_acc])],
+                                                                tables[id(read_partition[t_acc])], ccs_dict, getattr(params, "max_phred_q_trusted", None))
         p_values[c_acc][t_acc] = _result(c_acc, t_acc, C[t_acc], delta_t, p_value, range(n_support), used, bool(ccs_dict))[2:]
     return p_values
 
