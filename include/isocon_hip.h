@@ -394,7 +394,32 @@ int isocon_hw_pairs_wide(isocon_store *s, const uint32_t *q, const uint32_t *t, 
  *                                i in [-ref_len, 0) counts from the end as a Python index does; any other i outside [0, ref_len) is
  *                                ISOCON_E_ARG (the per-read statement raises IndexError) unless the table has no rows.  u_v and the
  *                                snippet length are not limited by the block size.
- *   isocon_readtab_device_bytes  device memory the handle holds.
+ *   isocon_readtab_set_qualities attaches base qualities (FASTQ input) to the table set: row r owns the record qual[qual_ptr[r] ..
+ *                                qual_ptr[r + 1]) (its length is rec_len), the read of row r starts at rec_start[r] in it (CCS.seq.index,
+ *                                modules/ccs_info.py:37-56).  Uploads them and fills, per row and 64-column block, the mask of gap columns
+ *                                of the read's row and the count of read bases before the block (k_rt_read_prefix).  These buffers exist
+ *                                only after this call; a second call replaces the first.  ISOCON_E_ARG: a quality above 93, offsets
+ *                                that descend (the handle keeps what it had).
+ *   isocon_readtab_quality       the queries of isocon_readtab_support (same arrays, same wrapping and refusal of coordinates; snippets
+ *                                for BOTH kinds) answered with one byte per (variant, row): out_codes[code_ptr[q] + v rows + j] for the
+ *                                v-th variant of query q and row j of its table; the caller sizes the range (code_ptr[q + 1] -
+ *                                code_ptr[q] >= variants x rows, code_ptr[0] = 0; spare bytes come back 0).  The byte restates
+ *                                get_read_ccs_probabilities_c / _t (modules/functions.py:240-331 kind 0, :334-433 kind 1) up to the
+ *                                quality they look up.  pos = column of candidate base i; shows_own = no differing column in
+ *                                [pos - 1, pos + u_v]; shows_other = the window of isocon_readtab_support's kind 1 equals the snippet,
+ *                                "insertion style" (2 before, u_v after) when the type is 'D' (kind 0) / 'I' (kind 1); seen = read
+ *                                bases in the read's row up to and including pos; read_coord = seen - 1 if shows_own, else seen + off
+ *                                with off = 0 for 'I' and -1 otherwise (kind 0), 0 for 'D', -2 for 'I' and -1 otherwise (kind 1);
+ *                                coord = rec_start + read_coord, then as CCS.read_aln_to_ccs_coord and a Python list index do:
+ *                                coord > rec_len is "beyond", coord == rec_len takes coord - 1, coord < 0 takes coord + rec_len, a
+ *                                result outside [0, rec_len) is "index".
+ *                                  0 .. 93  the quality at coord          0xFF  neither row is shown (the read is not informative)
+ *                                  0xFE     both are shown                0xFD  beyond the record (the reference exits)
+ *                                  0xFC     index out of range (the reference raises IndexError)
+ *                                both > neither > beyond > index > quality.  A byte depends on its own (variant, row) only: dropping a
+ *                                read at an earlier variant, and raising for a read that is still informative, is the caller's.
+ *                                ISOCON_E_ARG: no qualities attached.
+ *   isocon_readtab_device_bytes  device memory the handle holds (the qualities' buffers included).
  */
 typedef struct isocon_readtab isocon_readtab;
 int isocon_readtab_create(const uint8_t *ref_rows, const uint8_t *read_rows, const uint64_t *row_ptr, uint32_t n_rows, const uint32_t *first_row,
@@ -402,6 +427,10 @@ int isocon_readtab_create(const uint8_t *ref_rows, const uint8_t *read_rows, con
 int isocon_readtab_support(isocon_readtab *h, uint32_t n_queries, const uint32_t *q_table, const uint8_t *q_kind, const uint64_t *var_ptr,
                            const int32_t *var_pos, const int32_t *var_u, const uint8_t *var_type, const uint64_t *snip_ptr, const uint8_t *snip_bytes,
                            const uint64_t *bits_ptr, uint64_t *out_bits, uint32_t *out_count, float *kernel_ms);
+int isocon_readtab_set_qualities(isocon_readtab *h, const uint8_t *qual, const uint64_t *qual_ptr, const uint32_t *rec_start, float *kernel_ms);
+int isocon_readtab_quality(isocon_readtab *h, uint32_t n_queries, const uint32_t *q_table, const uint8_t *q_kind, const uint64_t *var_ptr,
+                           const int32_t *var_pos, const int32_t *var_u, const uint8_t *var_type, const uint64_t *snip_ptr, const uint8_t *snip_bytes,
+                           const uint64_t *code_ptr, uint8_t *out_codes, float *kernel_ms);
 void isocon_readtab_destroy(isocon_readtab *h);
 uint64_t isocon_readtab_device_bytes(const isocon_readtab *h);
 

@@ -8,6 +8,11 @@
 //   k_rt_support  one wavefront per query (one side of one edge), the rows of its table on the lanes in steps of 64; the variant list
 //                 is wave-uniform.  A lane finds the block of the variant's candidate base in its row's prefix counts, the column by a
 //                 select inside the block's word, and compares its window (reads of c: no differing column; reads of t: the snippet).
+//   k_rt_read_prefix  (table sets with base qualities) one wavefront per row, 64 columns per step: the gap mask of the read's row is a
+//                 ballot, the count of read bases before a block a running popcount.
+//   k_rt_quality  one wavefront per query as in k_rt_support; per variant every lane writes one byte, rt_quality_code of its row: the
+//                 quality at the variant's place in the read's record or the reason there is none.  The 64 bytes of a wavefront
+//                 and variant are one contiguous run.
 // No LDS, no scratch; lane 0 writes a wavefront's words.
 #pragma once
 #include "common.hpp"
@@ -33,8 +38,16 @@ struct RtQueries {
     const uint8_t *var_type;
     const uint64_t *snip_ptr;
     const uint8_t *snip_bytes;
-    const uint64_t *bits_ptr;
+    const uint64_t *out_ptr;          // k_rt_support: first word of the query's bit set, k_rt_quality: first byte of its codes
     uint32_t n;
+};
+
+struct RtQualities {                  // what isocon_readtab_set_qualities adds to a table set
+    const uint64_t *rgap;             // per block (readtab_core.hpp)
+    const uint32_t *rpre;             // per block
+    const uint8_t *qual;              // the records' qualities
+    const uint64_t *qual_ptr;         // n_rows + 1: qualities before row r's record
+    const uint32_t *rec_start;        // n_rows: where the read starts in its record
 };
 
 ISO_HD bool rt_symbol_ok(uint8_t ch) { return ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T' || ch == '-'; }
@@ -95,7 +108,7 @@ __global__ __launch_bounds__(256) void k_rt_support(RtTables T, RtQueries Q, uin
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t k = Q.q_table[q];
     const uint32_t r0 = T.first_row[k], nr = T.first_row[k + 1] - r0;
-    const uint64_t v0 = Q.var_ptr[q], v1 = Q.var_ptr[q + 1], w0 = Q.bits_ptr[q];
+    const uint64_t v0 = Q.var_ptr[q], v1 = Q.var_ptr[q + 1], w0 = Q.out_ptr[q];
     const bool snippets = Q.q_kind[q] != 0;
     uint32_t count = 0;
     for (uint32_t step = 0; step * 64 < nr; ++step) {
@@ -115,6 +128,50 @@ __global__ __launch_bounds__(256) void k_rt_support(RtTables T, RtQueries Q, uin
         count += (uint32_t)popc64(word);
     }
     if (lane == 0) out_count[q] = count;
+}
+
+__global__ __launch_bounds__(256) void k_rt_read_prefix(const uint8_t *__restrict__ read, const uint64_t *__restrict__ row_ptr, const uint64_t *__restrict__ blk_ptr,
+                                                         uint32_t n_rows, uint64_t *__restrict__ rgap, uint32_t *__restrict__ rpre)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n_rows) return;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t off = row_ptr[r], blk0 = blk_ptr[r];
+    const int64_t len = (int64_t)(row_ptr[r + 1] - off);
+    const int64_t nb = (len + 63) >> 6;
+    uint32_t bases = 0;
+    for (int64_t b = 0; b < nb; ++b) {
+        const int64_t col = b * 64 + lane;
+        const int n = len - b * 64 < 64 ? (int)(len - b * 64) : 64;
+        const uint64_t gb = __ballot(col < len && read[off + col] == '-');
+        if (lane == 0) {
+            rgap[blk0 + b] = gb;
+            rpre[blk0 + b] = bases;
+        }
+        bases += (uint32_t)popc64(~gb & rt_low_mask(n));
+    }
+}
+
+// out_codes[out_ptr[q] + v nr + j]: variant v (0-based in the query) and row j of the query's table of nr rows
+__global__ __launch_bounds__(256) void k_rt_quality(RtTables T, RtQualities U, RtQueries Q, uint8_t *__restrict__ out_codes)
+{
+    const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= Q.n) return;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t k = Q.q_table[q];
+    const uint32_t r0 = T.first_row[k], nr = T.first_row[k + 1] - r0;
+    const uint64_t v0 = Q.var_ptr[q], v1 = Q.var_ptr[q + 1], c0 = Q.out_ptr[q];
+    const int kind = Q.q_kind[q];
+    for (uint32_t j = lane; j < nr; j += 64) {
+        const uint64_t r = (uint64_t)r0 + j;
+        const uint64_t off = T.row_ptr[r], blk0 = T.blk_ptr[r], q0 = U.qual_ptr[r];
+        const RtRow R{T.nob + blk0, T.diff + blk0, T.pre + blk0, T.read + off, (uint32_t)(T.blk_ptr[r + 1] - blk0), (int64_t)(T.row_ptr[r + 1] - off), U.rgap + blk0,
+                      U.rpre + blk0};
+        const int64_t rec_len = (int64_t)(U.qual_ptr[r + 1] - q0), rec_start = U.rec_start[r];
+        for (uint64_t v = v0; v < v1; ++v)
+            out_codes[c0 + (v - v0) * nr + j] = rt_quality_code(R, Q.var_pos[v], Q.var_u[v], Q.var_type[v], kind, Q.snip_bytes + Q.snip_ptr[v],
+                                                                Q.snip_ptr[v + 1] - Q.snip_ptr[v], U.qual + q0, rec_len, rec_start);
+    }
 }
 
 }  // namespace isocon

@@ -6,7 +6,10 @@
 //     nob   bit c set: column c holds NO candidate base (A is '-' there, or the column lies past the row's end),
 //     diff  bit c set: A and B differ in column c (0 past the end),
 //     pre   candidate bases of A in the blocks before this one,
-// and the bytes of B.  What the per-read statements of the reference compute from the strings
+// and the bytes of B.  A table set with base qualities attached (isocon_readtab_set_qualities) also keeps
+//     rgap  bit c set: B is '-' in column c (0 past the end),
+//     rpre  read bases of B in the blocks before this one,
+// from which the number of read bases up to a column -- and with it the place of a variant in the read's quality record -- follows.  What the per-read statements of the reference compute from the strings
 // (modules/functions.py:149-201 get_support, :495-522 read_errors_from_alignment) becomes:
 //     column of candidate base i      block b = the last one with pre[b] <= i, then the (i - pre[b])-th zero bit of nob[b]
 //     aln_read[lo:hi] == aln_c[lo:hi]  no bit of diff in the columns [lo, hi)
@@ -111,6 +114,8 @@ struct RtRow {
     const uint8_t *read;          // len bytes of B
     uint32_t nb;
     int64_t len;
+    const uint64_t *rgap = nullptr;          // nb words   } only with qualities attached (rt_read_bases_upto, rt_quality_code)
+    const uint32_t *rpre = nullptr;          // nb counts  }
 };
 
 // column of candidate base i, 0 <= i < number of candidate bases of the row
@@ -132,20 +137,21 @@ ISO_HD bool rt_any_diff(const RtRow &R, int64_t lo, int64_t hi)
     return false;
 }
 
-// _ReadTable.agree_with_candidate for one variant: no differing column in [pos - 1, pos + u_v] within the row
-ISO_HD bool rt_agrees(const RtRow &R, uint32_t i, int32_t u_v)
+// no differing column in [pos - 1, pos + u_v] within the row (pos: a column of the row)
+ISO_HD bool rt_agrees_at(const RtRow &R, int64_t pos, int32_t u_v)
 {
-    const int64_t pos = rt_column_of(R, i);
     const int64_t lo = pos - 1 > 0 ? pos - 1 : 0;
     int64_t hi = pos + (int64_t)u_v + 1;
     if (hi > R.len) hi = R.len;
     return !rt_any_diff(R, lo, hi);
 }
 
-// _ReadTable.show_snippets for one variant: the read's row shows the snippet in its (clipped) window
-ISO_HD bool rt_shows(const RtRow &R, uint32_t i, int32_t u_v, bool is_insertion, const uint8_t *snippet, uint64_t snippet_len)
+// _ReadTable.agree_with_candidate for one variant: the window around the column of candidate base i
+ISO_HD bool rt_agrees(const RtRow &R, uint32_t i, int32_t u_v) { return rt_agrees_at(R, rt_column_of(R, i), u_v); }
+
+// the read's row shows the snippet in its (clipped) window around column pos: [pos - 2, pos + u_v) "insertion style", else [pos - 1, pos + u_v]
+ISO_HD bool rt_shows_at(const RtRow &R, int64_t pos, int32_t u_v, bool is_insertion, const uint8_t *snippet, uint64_t snippet_len)
 {
-    const int64_t pos = rt_column_of(R, i);
     const int64_t before = is_insertion ? 2 : 1, after = is_insertion ? (int64_t)u_v : (int64_t)u_v + 1;
     const int64_t lo = pos - before > 0 ? pos - before : 0;
     const int64_t hi = pos + after < R.len ? pos + after : R.len;
@@ -154,6 +160,52 @@ ISO_HD bool rt_shows(const RtRow &R, uint32_t i, int32_t u_v, bool is_insertion,
     for (int64_t j = 0; j < width; ++j)
         if (R.read[lo + j] != snippet[j]) return false;
     return true;
+}
+
+// _ReadTable.show_snippets for one variant
+ISO_HD bool rt_shows(const RtRow &R, uint32_t i, int32_t u_v, bool is_insertion, const uint8_t *snippet, uint64_t snippet_len)
+{
+    return rt_shows_at(R, rt_column_of(R, i), u_v, is_insertion, snippet, snippet_len);
+}
+
+// ---- base qualities: functions._ccs_probabilities (reference modules/functions.py:240-433) up to the quality it looks up ----
+
+// _ReadTable.read_bases_upto: read bases in aln_read[:pos + 1], 0 <= pos < len
+ISO_HD int64_t rt_read_bases_upto(const RtRow &R, int64_t pos)
+{
+    const int64_t b = pos >> 6;
+    return (int64_t)R.rpre[b] + popc64(~R.rgap[b] & rt_low_mask((int)(pos & 63) + 1));
+}
+
+// What one read says at one variant, as a byte: its quality 0 .. 93 at the variant, or why there is none.
+enum : uint8_t {
+    RT_Q_INDEX = 0xFC,            // the place lies outside the quality record (the per-read statement raises IndexError)
+    RT_Q_BEYOND = 0xFD,           // ... more than one past its end (CCS.read_aln_to_ccs_coord exits)
+    RT_Q_BOTH = 0xFE,             // the read shows its own sequence AND the other one (the per-read statement asserts)
+    RT_Q_NEITHER = 0xFF           // the read shows neither: not informative
+};
+
+// kind 0: a read of c judged against t (the shifted variant type is 'D'), kind 1: a read of t against c ('I').  qual: the read's
+// record of rec_len qualities, the read starts at rec_start in it.  Both > neither > beyond > index > the quality.
+ISO_HD uint8_t rt_quality_code(const RtRow &R, uint32_t i, int32_t u_v, uint8_t v_type, int kind, const uint8_t *snippet, uint64_t snippet_len, const uint8_t *qual,
+                               int64_t rec_len, int64_t rec_start)
+{
+    const int64_t pos = rt_column_of(R, i);
+    const bool shows_own = rt_agrees_at(R, pos, u_v);
+    const bool shows_other = rt_shows_at(R, pos, u_v, v_type == (kind ? 'I' : 'D'), snippet, snippet_len);
+    if (shows_own && shows_other) return RT_Q_BOTH;
+    if (!shows_own && !shows_other) return RT_Q_NEITHER;
+    const int64_t seen = rt_read_bases_upto(R, pos);
+    int64_t off = -1;          // place of the judged base relative to the bases seen, for a read that shows the other sequence
+    if (kind == 0 && v_type == 'I') off = 0;
+    if (kind == 1 && v_type == 'D') off = 0;
+    if (kind == 1 && v_type == 'I') off = -2;
+    int64_t coord = rec_start + (shows_own ? seen - 1 : seen + off);          // CCS.read_aln_to_ccs_coord, then a Python list index
+    if (coord > rec_len) return RT_Q_BEYOND;
+    if (coord == rec_len) coord -= 1;
+    if (coord < 0) coord += rec_len;
+    if (coord < 0 || coord >= rec_len) return RT_Q_INDEX;
+    return qual[coord];
 }
 
 }  // namespace isocon

@@ -11,7 +11,8 @@ alignments) that carry all of them; bound the probability of that many supporter
 The reference aligns the two orders of every edge one call at a time (or one Pool task per edge); here ALL edges of a
 round go to the GPU as one batch of isocon_sg_strings_batch (2 x edges alignments), everything after that is string
 bookkeeping on the host as in the reference.  With base qualities (a `ccs_dict`: FASTQ input) the error probabilities
-come from the qualities (functions.get_read_ccs_probabilities_c / _t), computed on the same read tables."""
+come from the qualities (functions.get_read_ccs_probabilities_c / _t): which quality a read contributes at a variant is
+looked up on the same read tables (isocon_readtab_quality on the device tables), the floats stay on the host."""
 from __future__ import annotations
 
 import ctypes
@@ -131,36 +132,54 @@ class _ReadTable(object):
         return [raw[o[r]:o[r + 1]].replace("-", "") for r in range(self.n)]
 
 
-def _ccs_probabilities_on_table(tab, variant_coords, other_snippets, ccs_dict, ratios, max_phred_q_trusted, shifted_type, coord_when_other):
-    """functions._ccs_probabilities for all reads of a table at once: (informative mask, probability per read)."""
+# What one read says at one variant, as a byte (csrc/readtab_core.hpp rt_quality_code): its quality 0 .. 93 there, or
+_Q_INDEX, _Q_BEYOND, _Q_BOTH, _Q_NEITHER = 0xFC, 0xFD, 0xFE, 0xFF
+
+
+def _quality_codes_on_table(tab, i, v_type, u_v, alive, other_snippet, ccs_dict, shifted_type, coord_when_other):
+    """the code byte of every read of a host table at one variant (alive: the reads still informative, for column_of's IndexError)"""
+    flat, qoff, rec_len, rec_start = tab.qualities(ccs_dict)
+    pos = tab.column_of(i, alive)
+    shows_own = tab.own_window_equal(pos, u_v)
+    if v_type == shifted_type:
+        shows_other = tab.window_equals(pos, 2, u_v, other_snippet)
+    else:
+        shows_other = tab.window_equals(pos, 1, u_v + 1, other_snippet)
+    seen = tab.read_bases_upto(pos)
+    read_coord = np.where(shows_own, seen - 1, seen + coord_when_other.get(v_type, -1))
+    coord = rec_start + read_coord                     # CCS.read_aln_to_ccs_coord
+    beyond = coord > rec_len
+    coord = np.where(coord == rec_len, coord - 1, coord)
+    coord = np.where(coord < 0, coord + rec_len, coord)        # a negative list index counts from the end
+    outside = (coord < 0) | (coord >= rec_len)
+    q = flat[np.clip(qoff + np.clip(coord, 0, np.maximum(rec_len - 1, 0)), 0, max(len(flat) - 1, 0))] if len(flat) else np.zeros(tab.n, dtype=np.int64)
+    code = np.clip(q, 0, 93)
+    code = np.where(outside, _Q_INDEX, code)
+    code = np.where(beyond, _Q_BEYOND, code)
+    code = np.where(~shows_own & ~shows_other, _Q_NEITHER, code)
+    return np.where(shows_own & shows_other, _Q_BOTH, code).astype(np.uint8)
+
+
+def _ccs_probabilities_from_codes(n, variant_coords, code_of, ratios, max_phred_q_trusted):
+    """functions._ccs_probabilities for the n reads of a table at once: (informative mask, probability per read).  code_of(v, i, v_type,
+    u_v, alive) gives the reads' code bytes at the v-th variant: _quality_codes_on_table on the host tables, a row of
+    isocon_readtab_quality's answer on the device tables.  Every float statement of the quality route is here."""
     subs_ratio, ins_ratio, del_ratio = ratios
     assert len(variant_coords) > 0
-    alive = np.ones(tab.n, dtype=bool)
-    prob = np.ones(tab.n, dtype=np.float64)
-    if tab.n == 0:
+    alive = np.ones(n, dtype=bool)
+    prob = np.ones(n, dtype=np.float64)
+    if n == 0:
         return alive, prob
-    flat, qoff, rec_len, rec_start = tab.qualities(ccs_dict)
     base = np.asarray([10 ** (-((q - 3) * (max_phred_q_trusted - 3.0) / (90.0) + 3) / 10.0) for q in range(94)], dtype=np.float64)
-    for i, (v_type, _, u_v) in variant_coords.items():
-        pos = tab.column_of(i, alive)
-        shows_own = tab.own_window_equal(pos, u_v)
-        if v_type == shifted_type:
-            shows_other = tab.window_equals(pos, 2, u_v, other_snippets[i])
-        else:
-            shows_other = tab.window_equals(pos, 1, u_v + 1, other_snippets[i])
-        assert not (alive & shows_own & shows_other).any()
-        seen = tab.read_bases_upto(pos)
-        read_coord = np.where(shows_own, seen - 1, seen + coord_when_other.get(v_type, -1))
-        alive &= shows_own | shows_other
-        coord = rec_start + read_coord                     # CCS.read_aln_to_ccs_coord
-        if (alive & (coord > rec_len)).any():
+    for v, (i, (v_type, _, u_v)) in enumerate(variant_coords.items()):
+        code = code_of(v, i, v_type, u_v, alive)
+        assert not (alive & (code == _Q_BOTH)).any()
+        alive &= code != _Q_NEITHER
+        if (alive & (code == _Q_BEYOND)).any():
             raise SystemExit("Index error: read position beyond its quality record")
-        coord = np.where(coord == rec_len, coord - 1, coord)
-        coord = np.where(coord < 0, coord + rec_len, coord)        # a negative list index counts from the end
-        if (alive & ((coord < 0) | (coord >= rec_len))).any():
+        if (alive & (code == _Q_INDEX)).any():
             raise IndexError("list index out of range")
-        q = flat[np.clip(qoff + np.clip(coord, 0, np.maximum(rec_len - 1, 0)), 0, max(len(flat) - 1, 0))]
-        p10 = base[np.clip(q, 0, 93)]
+        p10 = base[np.minimum(code, 93)]
         if u_v > 1:
             p_error = p10
         elif v_type == "S":
@@ -172,6 +191,14 @@ def _ccs_probabilities_on_table(tab, variant_coords, other_snippets, ccs_dict, r
         prob = np.where(alive, prob * p_error, prob)
     assert ((prob[alive] > 0.0) & (prob[alive] < 1.0)).all()
     return alive, prob
+
+
+def _ccs_probabilities_on_table(tab, variant_coords, other_snippets, ccs_dict, ratios, max_phred_q_trusted, shifted_type, coord_when_other, codes=None):
+    """_ccs_probabilities_from_codes for a table: a device table brings its codes (variants x reads), a host table computes them"""
+    if codes is not None:
+        return _ccs_probabilities_from_codes(tab.n, variant_coords, lambda v, i, v_type, u_v, alive: codes[v], ratios, max_phred_q_trusted)
+    return _ccs_probabilities_from_codes(tab.n, variant_coords, lambda v, i, v_type, u_v, alive: _quality_codes_on_table(
+        tab, i, v_type, u_v, alive, other_snippets[i], ccs_dict, shifted_type, coord_when_other), ratios, max_phred_q_trusted)
 
 
 def _variants_of(aln_t, aln_c):
@@ -314,7 +341,7 @@ def _tables_for(wanted, cache=None, build=None):
 # ---- the read tables on the device (isocon_readtab_*: csrc/readtab.hpp) ----
 # The integer work of a test -- the column of a candidate position in every read's alignment, the window comparisons, the error
 # counts -- for all edges of a round in one call per table set; the probabilities and the bound stay on the host (_test_on_supporters).
-DEVICE_STATS = {"create_calls": 0, "rows_uploaded": 0, "support_calls": 0, "queries": 0, "kernel_ms": 0.0}
+DEVICE_STATS = {"create_calls": 0, "rows_uploaded": 0, "support_calls": 0, "queries": 0, "quality_attach_calls": 0, "quality_calls": 0, "kernel_ms": 0.0}
 _HAS_DEVICE = None
 
 
@@ -345,14 +372,51 @@ def _ptr(a, typ):
 class _DeviceSet(object):
     """One isocon_readtab handle: the tables of up to 2048 candidates.  Freed by clear_tables(), or with its last table."""
 
-    def __init__(self, handle):
+    def __init__(self, handle, accs=(), read_rows=()):
         self.handle = handle
         self.bytes = int(_lib.lib().isocon_readtab_device_bytes(handle))
+        self.accs, self.read_rows = accs, read_rows          # per row: the read's accession and its gapped row (the stored string itself)
+        self.qual_of, self.qual_ok = None, False             # the ccs_dict whose qualities are attached; False: they cannot be (host tables)
+
+    def attach_qualities(self, ccs_dict):
+        """the base qualities of the set's reads (ccs_dict[acc].qual) onto the device, once per ccs_dict: one isocon_readtab_set_qualities.
+        Returns False -- the set's edges then go through the host tables, which raise what there is to raise -- when a record is
+        missing, does not hold its read, or does not have one quality 0 .. 93 per base."""
+        if self.qual_of is ccs_dict:
+            return self.qual_ok
+        self.qual_of, self.qual_ok = ccs_dict, False
+        n = len(self.accs)
+        try:
+            recs = [ccs_dict[acc] for acc in self.accs]
+            start = np.fromiter((r.seq.index(row.replace("-", "")) for r, row in zip(recs, self.read_rows)), dtype=np.int64, count=n)
+        except (KeyError, ValueError):
+            return False
+        for r in recs:                                  # the record's quality list as an array, made once per record
+            if getattr(r, "_qual_np_of", None) is not r.qual:
+                r._qual_np, r._qual_np_of = np.asarray(r.qual, dtype=np.int64), r.qual
+        if any(len(r.seq) != len(r._qual_np) for r in recs):
+            return False
+        flat = np.concatenate([r._qual_np for r in recs]) if recs else np.zeros(0, dtype=np.int64)
+        if len(flat) and (flat.min() < 0 or flat.max() > 93):
+            return False
+        qual_ptr = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(np.fromiter((len(r._qual_np) for r in recs), dtype=np.uint64, count=n), out=qual_ptr[1:])
+        qual = flat.astype(np.uint8) if len(flat) else np.zeros(1, dtype=np.uint8)
+        rec_start = start.astype(np.uint32) if n else np.zeros(1, dtype=np.uint32)
+        ms = ctypes.c_float(0.0)
+        _lib.check(_lib.lib().isocon_readtab_set_qualities(self.handle, _ptr(qual, _lib.u8p), _ptr(qual_ptr, _lib.u64p), _ptr(rec_start, _lib.u32p), ctypes.byref(ms)),
+                   "isocon_readtab_set_qualities")
+        DEVICE_STATS["quality_attach_calls"] += 1
+        DEVICE_STATS["kernel_ms"] += ms.value
+        self.bytes = int(_lib.lib().isocon_readtab_device_bytes(self.handle))
+        self.qual_ok = True
+        return True
 
     def free(self):
         if self.handle is not None:
             _lib.lib().isocon_readtab_destroy(self.handle)
             self.handle, self.bytes = None, 0
+            self.qual_of, self.qual_ok = None, False
 
     def __del__(self):
         try:
@@ -363,7 +427,7 @@ class _DeviceSet(object):
 
 class _DeviceTable(object):
     """table k of a set: what _test_on_supporters needs on the host (sizes and error counts), the rest lives in the set"""
-    __slots__ = ("set", "k", "n", "ref_len", "ins", "dele", "sub")
+    __slots__ = ("set", "k", "n", "ref_len", "ins", "dele", "sub", "accs")
 
 
 def _pack_rows(items):
@@ -396,20 +460,21 @@ def _build_device_tables(items):
     DEVICE_STATS["create_calls"] += 1
     DEVICE_STATS["rows_uploaded"] += n
     DEVICE_STATS["kernel_ms"] += ms.value
-    dset = _DeviceSet(handle)
+    dset = _DeviceSet(handle, [acc for _, ra in items for acc in ra], [v[1] for _, ra in items for v in ra.values()])
     errors = errors[:n].astype(np.int64)
     tables = []
     for k, (ref_len, _) in enumerate(items):
         r0, r1 = int(first_row[k]), int(first_row[k + 1])
         t = _DeviceTable()
         t.set, t.k, t.n, t.ref_len = dset, k, r1 - r0, ref_len
+        t.accs = dset.accs[r0:r1]
         t.ins, t.dele, t.sub = errors[r0:r1, 0], errors[r0:r1, 1], errors[r0:r1, 2]
         tables.append(t)
     return tables
 
 
 def _pack_queries(queries):
-    """[(table index, kind, variant_coords, snippets or None, rows of the table)] as isocon_readtab_support takes them: (q_table,
+    """[(table index, kind, variant_coords, snippets or None, rows of the table)] as isocon_readtab_support / _quality take them: (q_table,
     q_kind, var_ptr, var_pos, var_u, var_type, snip_ptr, snip_bytes, bits_ptr)"""
     q_table, q_kind, var_ptr, var_pos, var_u, var_type, snip_len, snips, bits_ptr = [], [], [0], [], [], [], [], [], [0]
     for k, kind, coords, snippets, n_rows in queries:
@@ -419,7 +484,7 @@ def _pack_queries(queries):
             var_pos.append(i)
             var_u.append(u_v)
             var_type.append(ord(v_type))
-            text = snippets[i] if kind else ""
+            text = snippets[i] if snippets is not None else ""
             snips.append(text)
             snip_len.append(len(text))
         var_ptr.append(len(var_pos))
@@ -462,14 +527,32 @@ def _device_support(handle, queries):
     return out
 
 
+def _device_quality(handle, queries):
+    """one isocon_readtab_quality call: the code bytes (variants x rows, uint8) of every query of _pack_queries (snippets for both kinds)"""
+    if not queries:
+        return []
+    q_table, q_kind, var_ptr, var_pos, var_u, var_type, snip_ptr, snip_bytes, _ = _pack_queries(queries)
+    code_ptr = np.zeros(len(queries) + 1, dtype=np.uint64)
+    np.cumsum(np.asarray([len(coords) * n_rows for _, _, coords, _, n_rows in queries], dtype=np.uint64), out=code_ptr[1:])
+    codes = np.zeros(max(int(code_ptr[-1]), 1), dtype=np.uint8)
+    ms = ctypes.c_float(0.0)
+    _lib.check(_lib.lib().isocon_readtab_quality(handle, len(queries), _ptr(q_table, _lib.u32p), _ptr(q_kind, _lib.u8p), _ptr(var_ptr, _lib.u64p),
+                                                 _ptr(var_pos, _lib.i32p), _ptr(var_u, _lib.i32p), _ptr(var_type, _lib.u8p), _ptr(snip_ptr, _lib.u64p),
+                                                 _ptr(snip_bytes, _lib.u8p), _ptr(code_ptr, _lib.u64p), _ptr(codes, _lib.u8p), ctypes.byref(ms)), "isocon_readtab_quality")
+    DEVICE_STATS["quality_calls"] += 1
+    DEVICE_STATS["kernel_ms"] += ms.value
+    return [codes[int(code_ptr[q]):int(code_ptr[q + 1])].reshape(len(coords), n_rows) for q, (_, _, coords, _, n_rows) in enumerate(queries)]
+
+
 def _in_range(coords, ref_len):
     return all(-ref_len <= i < ref_len for i in coords)
 
 
-def _tests_on_device(live, of_edge, C, read_partition):
-    """{edge: (variant_coords_t, p_value, supporting reads, reads used)} for the edges of a round (no base qualities): supporters and
-    error counts from the device tables, one support call per table set.  An edge with a variant coordinate that the per-read
-    statement cannot index stays on the host tables, where it raises as it always did."""
+def _tests_on_device(live, of_edge, C, read_partition, ccs_dict=None, max_phred_q_trusted=None):
+    """{edge: (variant_coords_t, p_value, supporting reads, reads used)} for the edges of a round: supporters and error counts from the
+    device tables, one support call per table set; with base qualities (ccs_dict) also every read's quality code at every variant, one
+    quality call per table set.  An edge with a variant coordinate that the per-read statement cannot index stays on the host tables,
+    where it raises as it always did; so does an edge of a table set whose qualities cannot be attached."""
     prepared, on_host = {}, []
     for e in live:
         c_acc, t_acc = e
@@ -479,26 +562,38 @@ def _tests_on_device(live, of_edge, C, read_partition):
         else:
             on_host.append(e)
     tables = _tables_for([(C[acc], read_partition[acc]) for e in prepared for acc in e], _DEVICE_TABLES, _build_device_tables)
-    by_set = {}          # id(set) -> (set, its queries, where each answer goes)
+    if ccs_dict:
+        for e in list(prepared):
+            if not all(tables[id(read_partition[acc])].set.attach_qualities(ccs_dict) for acc in e):
+                del prepared[e]
+                on_host.append(e)
+    by_set = {}          # id(set) -> (set, its support queries, where each answer goes, its quality queries, where each answer goes)
     for e, ev in prepared.items():
         tab_c, tab_t = tables[id(read_partition[e[0]])], tables[id(read_partition[e[1]])]
-        for side, tab, kind, coords, snippets in ((0, tab_c, 0, ev[2], None), (1, tab_t, 1, ev[1], ev[3])):
-            group = by_set.setdefault(id(tab.set), (tab.set, [], []))
+        for side, tab, kind, coords, snippets, others in ((0, tab_c, 0, ev[2], None, ev[4]), (1, tab_t, 1, ev[1], ev[3], ev[3])):
+            group = by_set.setdefault(id(tab.set), (tab.set, [], [], [], []))
             group[1].append((tab.k, kind, coords, snippets, tab.n))
             group[2].append((e, side))
-    supporters = {}
-    for dset, queries, where in by_set.values():
+            if ccs_dict and len(ev[0]) > 0:          # (no variants: the test looks at no quality)
+                group[3].append((tab.k, kind, coords, others, tab.n))
+                group[4].append((e, side))
+    supporters, codes = {}, {}
+    for dset, queries, where, quality_queries, quality_where in by_set.values():
         for key, sup in zip(where, _device_support(dset.handle, queries)):
             supporters[key] = sup
+        for key, code in zip(quality_where, _device_quality(dset.handle, quality_queries)):
+            codes[key] = code
     results = {}
     for e, ev in prepared.items():
         variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c = ev
         results[e] = _test_on_supporters(C[e[1]], variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c,
-                                         tables[id(read_partition[e[0]])], tables[id(read_partition[e[1]])], supporters[(e, 0)], supporters[(e, 1)])
+                                         tables[id(read_partition[e[0]])], tables[id(read_partition[e[1]])], supporters[(e, 0)], supporters[(e, 1)],
+                                         ccs_dict, max_phred_q_trusted, codes.get((e, 0)), codes.get((e, 1)))
     if on_host:
         host = _tables_for([(C[acc], read_partition[acc]) for e in on_host for acc in e])
         for e in on_host:
-            results[e] = _test_on_tables(C[e[1]], C[e[0]], of_edge[e][0], of_edge[e][1], host[id(read_partition[e[0]])], host[id(read_partition[e[1]])])
+            results[e] = _test_on_tables(C[e[1]], C[e[0]], of_edge[e][0], of_edge[e][1], host[id(read_partition[e[0]])], host[id(read_partition[e[1]])],
+                                         ccs_dict, max_phred_q_trusted)
     return results
 
 
@@ -518,9 +613,10 @@ def _test_on_tables(t_seq, c_seq, alignment_tc, alignment_ct, tab_c, tab_t, ccs_
 
 
 def _test_on_supporters(t_seq, variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c, tab_c, tab_t, sup_c, sup_t,
-                        ccs_dict=None, max_phred_q_trusted=None):
+                        ccs_dict=None, max_phred_q_trusted=None, codes_c=None, codes_t=None):
     """The test of an edge once the supporting reads are known (sup_c / sup_t: ascending row indices into the tables of c / t, host
-    or device tables alike): error probabilities per read and the bound."""
+    or device tables alike): error probabilities per read and the bound.  With base qualities, device tables bring codes_c / codes_t
+    (isocon_readtab_quality: variants x reads); host tables compute theirs."""
     n_support = len(sup_c) + len(sup_t)
     if len(variants) == 0:
         return variant_coords_t, 0.0, n_support, tab_c.n + tab_t.n
@@ -531,8 +627,9 @@ def _test_on_supporters(t_seq, variants, variant_coords_t, variant_coords_c, ali
         del_ = float(max(1.0, int(tab_t.dele.sum() + tab_c.dele.sum())))
         tot_errors = subs + ins + del_
         ratios = (subs / tot_errors, ins / tot_errors, del_ / tot_errors)
-        alive_c, prob_c = _ccs_probabilities_on_table(tab_c, variant_coords_c, alignment_t_to_c, ccs_dict, ratios, max_phred_q_trusted, "D", {"I": 0})
-        alive_t, prob_t = _ccs_probabilities_on_table(tab_t, variant_coords_t, alignment_c_to_t, ccs_dict, ratios, max_phred_q_trusted, "I", {"D": 0, "I": -2})
+        alive_c, prob_c = _ccs_probabilities_on_table(tab_c, variant_coords_c, alignment_t_to_c, ccs_dict, ratios, max_phred_q_trusted, "D", {"I": 0}, codes_c)
+        alive_t, prob_t = _ccs_probabilities_on_table(tab_t, variant_coords_t, alignment_c_to_t, ccs_dict, ratios, max_phred_q_trusted, "I", {"D": 0, "I": -2},
+                                                      codes_t)
         prob = np.concatenate([prob_c[alive_c], prob_t[alive_t]])
         if len(prob) == 0:
             assert n_support == 0
@@ -616,9 +713,9 @@ def do_statistical_tests_per_edge(nearest_neighbor_graph, C, X, read_partition, 
     alignments = SWM._align_pairs(pairs, [-3] * len(pairs), 2, 3, 1) if pairs else []
     of_edge = {e: (alignments[2 * i], alignments[2 * i + 1]) for i, e in enumerate(live)}
     p_values = {c_acc: {} for c_acc in nearest_neighbor_graph}
-    on_device = not ccs_dict and device_tables_enabled()
+    on_device = device_tables_enabled()
     if on_device:
-        done = _tests_on_device(live, of_edge, C, read_partition)
+        done = _tests_on_device(live, of_edge, C, read_partition, ccs_dict, getattr(params, "max_phred_q_trusted", None))
     else:
         tables = _tables_for([(C[acc], read_partition[acc]) for e in live for acc in e])
     for c_acc, t_acc in edges:
