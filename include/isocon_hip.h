@@ -435,6 +435,32 @@ void isocon_readtab_destroy(isocon_readtab *h);
 uint64_t isocon_readtab_device_bytes(const isocon_readtab *h);
 
 /*
+ * The variants of candidate-vs-reference edges of the hypothesis test from the alignments' CIGAR ops: what _candidate_vs_reference
+ * (modules/hypothesis_test_module.py:99-110), get_mask_start_and_end (modules/functions.py:218-236) and get_variant_coordinates (:89-146)
+ * compute on the two gapped strings of an alignment -- which never exist here (kernels: isocon_amd/csrc/edgevar.hpp).  Independent of a
+ * store: sequence s = seqs[seq_ptr[s] .. seq_ptr[s + 1]) (ASCII, ACGT; at most 2^30 bases), edge e = (reference edge_t[e], candidate edge_c[e]),
+ * both ids into seqs.  Its two alignments in isocon_sg_trace_batch's encoding: list 2 e = ops[ops_ptr[2 e] .. ops_ptr[2 e + 1]) aligns (t, c)
+ * (t is the query), list 2 e + 1 aligns (c, t).  The variants are the columns of ops other than '=' outside the leading and trailing gap run
+ * of either row ('=' against 'X' is trusted); the (c, t) list replaces the (t, c) one only with strictly fewer variants (out_flipped[e] = 1).
+ * The caller gives edge e the record slots rec_ptr[e] .. rec_ptr[e + 1) -- enough is the larger of its two lists' summed lengths of ops other
+ * than '=' -- and gets out_n_var[e] records of 8 int32 in out_recs[8 s ..], in column order:
+ *     column i, t_last, c_last (bases of t / c in aln[:i + 1], minus one), key on t, key on c ('D': t_last, c_last + 1; 'I': t_last + 1,
+ *     c_last; 'S': t_last, c_last), u_v, snippet length, type letter | p_t << 8 | p_c << 16 (the two rows' characters in column i)
+ * Every variant is there: filing them under their keys in this order gives the reference's dicts, overwritten entries and key order
+ * included.  Spare slots come back 0.  out_snip_ptr has rec_ptr[n_edges] - rec_ptr[0] + 1 entries: the snippets aln_c / aln_t[max(0, i - 1)
+ * : i + u_v + 1] of slot s are out_snip_c / out_snip_t[out_snip_ptr[s] .. out_snip_ptr[s + 1]).  The caller sizes the two byte buffers
+ * (snip_cap each); *n_snip_needed always returns the size needed, and ISOCON_E_CAPACITY means that everything but the snippet bytes is
+ * valid and the call has to be repeated with larger buffers.
+ * out_bad[e] = 1, and no record, for an edge one of whose lists does not consume exactly len(t) and len(c), uses a code above 3 or holds
+ * an op of length 0.  ISOCON_E_ARG (isocon_last_error names the first such edge): an id out of range, an empty sequence, offsets that
+ * descend, more variants than the edge's slots.  ISOCON_E_ALPHABET: a byte outside ACGT.  n_edges = 0 is ISOCON_OK.
+ */
+int isocon_edge_variants(const uint8_t *seqs, const uint64_t *seq_ptr, uint32_t n_seqs, uint32_t n_edges, const uint32_t *edge_t, const uint32_t *edge_c,
+                         const uint32_t *ops, const uint64_t *ops_ptr, const uint64_t *rec_ptr, uint8_t *out_flipped, uint32_t *out_n_var, uint8_t *out_bad,
+                         int32_t *out_recs, uint64_t *out_snip_ptr, uint8_t *out_snip_c, uint8_t *out_snip_t, uint64_t snip_cap, uint64_t *n_snip_needed,
+                         float *kernel_ms);
+
+/*
  * Greedy partition of the nearest-neighbour graph into consensus centres and their members, on integer ids: what
  * get_partitions_no_copy (modules/partitions.py:301-413, called by partition_strings :416-593 on nx.reverse(G_star)) and
  * partition_highest_reachable_with_edge_degrees (modules/end_invariant_functions.py:405-533; nbr_tiebreak = 0) compute on networkx

@@ -93,20 +93,23 @@ def ops_to_cigar(ops):
     return "".join("%d%s" % (op >> 4, _OPS[op & 15]) for op in ops)
 
 
-def _align_pairs(pairs, mismatch, match_score=2, opening_penalty=2, gap_ext=0, ed_upper=None, want_dict=False):
+def _align_pairs(pairs, mismatch, match_score=2, opening_penalty=2, gap_ext=0, ed_upper=None, want_dict=False, want_ops=False):
     """[(s1, s2)], per-pair mismatch penalties -> [(s1_aln, s2_aln, (matches, mismatches, indels))].
     mismatch None: the penalty of every pair from the error-rate bucket of its ed_upper (SWM:102-109).
     ed_upper: the pairs' edit distances where the caller has them (they only narrow the computed part of the matrix;
-    the device re-aligns in full whatever it cannot certify, see include/isocon_hip.h)."""
+    the device re-aligns in full whatever it cannot certify, see include/isocon_hip.h).
+    want_ops: the alignments as run-length ops only -- (ops uint32[], ops_ptr int64[len(pairs) + 1]), the ops that _ops_to_alignment turns
+    into the strings of the call without it (same penalties, same band hints; isocon_sg_trace_batch: no gapped string is made)."""
     if not pairs:
-        return ([], {}) if want_dict else []
+        return (np.zeros(0, dtype=np.uint32), np.zeros(1, dtype=np.int64)) if want_ops else ([], {}) if want_dict else []
     from . import perf_log
     with perf_log.call("SW_alignment_module.alignments", pairs=len(pairs), open=opening_penalty, ext=gap_ext, hints=ed_upper is not None):
-        return _align_pairs_impl(pairs, mismatch, match_score, opening_penalty, gap_ext, ed_upper, want_dict)
+        return _align_pairs_impl(pairs, mismatch, match_score, opening_penalty, gap_ext, ed_upper, want_dict, want_ops)
 
 
-def _align_pairs_impl(pairs, mismatch, match_score, opening_penalty, gap_ext, ed_upper, want_dict=False):
-    """want_dict: returns (alignments, {pairs[p][0]: {pairs[p][1]: alignments[p]}} or None when the helper module is missing)"""
+def _align_pairs_impl(pairs, mismatch, match_score, opening_penalty, gap_ext, ed_upper, want_dict=False, want_ops=False):
+    """want_dict: returns (alignments, {pairs[p][0]: {pairs[p][1]: alignments[p]}} or None when the helper module is missing);
+    want_ops: returns (ops, ops_ptr) and expands nothing"""
     st, a, b, owned = store_for_pairs(pairs)
     try:
         la, lb = st.lens[a], st.lens[b]
@@ -122,6 +125,10 @@ def _align_pairs_impl(pairs, mismatch, match_score, opening_penalty, gap_ext, ed
             # computes them first (isocon_ed_pairs, ~1e7 pairs/s) -- with a bound the alignment runs inside its certified band
             # (4-9x less work for related sequences) and comes out identical; unrelated pairs fall back to the full matrix
             ed_upper = st.ed_pairs(a, b, None)
+        if want_ops:
+            ops, ops_ptr, _ = st.sg_trace(a, b, np.asarray(mismatch, dtype=np.int8), match=match_score, open_=opening_penalty, ext=gap_ext, tie_policy=TIE_POLICY,
+                                          ed_upper=ed_upper)
+            return ops, ops_ptr
         aln_a, aln_b, ptr, res, ops, ops_ptr = st.sg_strings(a, b, np.asarray(mismatch, dtype=np.int8), match=match_score,
                                                              open_=opening_penalty, ext=gap_ext, tie_policy=TIE_POLICY,
                                                              return_ops=True, ed_upper=ed_upper)

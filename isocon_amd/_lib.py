@@ -103,6 +103,8 @@ SYMBOLS = {
     "isocon_readtab_quality": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, u32p, u8p, u64p, i32p, i32p, u8p, u64p, u8p, u64p, u8p, f32p]),
     "isocon_readtab_destroy": (None, [ctypes.c_void_p]),
     "isocon_readtab_device_bytes": (ctypes.c_uint64, [ctypes.c_void_p]),
+    "isocon_edge_variants": (ctypes.c_int, [u8p, u64p, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p, u32p, u64p, u64p, u8p, u32p, u8p, i32p, u64p, u8p, u8p,
+                                            ctypes.c_uint64, u64p, f32p]),
 }
 
 _lib = None

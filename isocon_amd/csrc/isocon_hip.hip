@@ -32,6 +32,7 @@
 #include "ed_bytes.hpp"
 #include "nn2_depth.hpp"
 #include "readtab.hpp"
+#include "edgevar.hpp"
 
 namespace isocon {
 thread_local std::string g_last_error;
@@ -135,6 +136,7 @@ enum {
     SLOT_HW_Q, SLOT_HW_T, SLOT_HW_K, SLOT_HW_OUT, SLOT_HW_TRACE, SLOT_HW_CTR, SLOT_HW_TILEQ, SLOT_HW_LANES, SLOT_HW_PQ, SLOT_HW_KEY, SLOT_HW_HIST, SLOT_HW_CURSOR, SLOT_HW_TBASE, SLOT_HW_CLS,
     SLOT_PACK_ASCII, SLOT_PACK_OFF, SLOT_PACK_BAD, SLOT_PACK_HIST, SLOT_PACK_FLAGS, SLOT_EB_A, SLOT_EB_B, SLOT_EB_K, SLOT_EB_OUT, SLOT_EB_ROWS, SLOT_SCAN_TMP, SLOT_SCAN_SUMS,
     SLOT_RT_REF, SLOT_RT_IN, SLOT_RT_OUT,
+    SLOT_EV_IN, SLOT_EV_OUT, SLOT_EV_SNIP,
     SLOT_COUNT
 };
 static_assert(SLOT_COUNT <= 160, "ScratchPool::slots too small");
@@ -1022,6 +1024,7 @@ extern "C" int isocon_block_bound_pairs(isocon_store *s, const uint32_t *owner, 
 #include "hw_host.inc"
 #include "hw_full_host.inc"
 #include "readtab_host.inc"
+#include "edgevar_host.inc"
 
 extern "C" int isocon_partition_ids(uint32_t n, const int32_t *degree, uint64_t n_edges, const uint32_t *edge_a, const uint32_t *edge_b,
                                     const uint32_t *rank, int32_t nbr_tiebreak, uint32_t *out_centre, int64_t *out_weight,

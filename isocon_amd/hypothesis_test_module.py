@@ -548,15 +548,17 @@ def _in_range(coords, ref_len):
     return all(-ref_len <= i < ref_len for i in coords)
 
 
-def _tests_on_device(live, of_edge, C, read_partition, ccs_dict=None, max_phred_q_trusted=None):
+def _tests_on_device(live, of_edge, C, read_partition, ccs_dict=None, max_phred_q_trusted=None, variants_of=None):
     """{edge: (variant_coords_t, p_value, supporting reads, reads used)} for the edges of a round: supporters and error counts from the
     device tables, one support call per table set; with base qualities (ccs_dict) also every read's quality code at every variant, one
     quality call per table set.  An edge with a variant coordinate that the per-read statement cannot index stays on the host tables,
-    where it raises as it always did; so does an edge of a table set whose qualities cannot be attached."""
+    where it raises as it always did; so does an edge of a table set whose qualities cannot be attached.  variants_of: {edge: the tuple
+    of _edge_variants} where the caller has them (_edge_variants_on_device); of_edge[e], the two gapped alignments, is then looked at
+    only for the edges that stay on the host tables (_LazyAlignments)."""
     prepared, on_host = {}, []
     for e in live:
         c_acc, t_acc = e
-        ev = _edge_variants(C[t_acc], C[c_acc], of_edge[e][0], of_edge[e][1])
+        ev = variants_of[e] if variants_of is not None else _edge_variants(C[t_acc], C[c_acc], of_edge[e][0], of_edge[e][1])
         if _in_range(ev[2], len(C[c_acc])) and _in_range(ev[1], len(C[t_acc])):
             prepared[e] = ev
         else:
@@ -595,6 +597,149 @@ def _tests_on_device(live, of_edge, C, read_partition, ccs_dict=None, max_phred_
             results[e] = _test_on_tables(C[e[1]], C[e[0]], of_edge[e][0], of_edge[e][1], host[id(read_partition[e[0]])], host[id(read_partition[e[1]])],
                                          ccs_dict, max_phred_q_trusted)
     return results
+
+
+# ---- the variants of the edges on the device (isocon_edge_variants: csrc/edgevar.hpp) ----
+# The candidate-vs-candidate alignments of a round stay run-length ops: which columns are variants, where they lie on t and on c, u_v and the
+# snippets come from one call per round (per EDGE_VARIANT_BATCH edges); the gapped strings of an edge are made only if something asks.
+EDGE_VARIANT_STATS = {"calls": 0, "edges": 0, "kernel_ms": 0.0, "lazy_expansions": 0}
+EDGE_VARIANT_BATCH = 4096
+
+
+def edge_variants_on_device_enabled():
+    """the variants of a round's edges come from the device: the device tables are on and ISOCON_DEBUG_VARIANT=stat_host_variants is not set"""
+    return device_tables_enabled() and not _variant_listed("stat_host_variants")
+
+
+class _LazyAlignments(object):
+    """of_edge for a round whose alignments are ops: e -> ((aln_t, aln_c), (aln_c, aln_t)) of the (t, c) and the (c, t) alignment, expanded
+    when asked for (EDGE_VARIANT_STATS["lazy_expansions"] counts the edges)"""
+
+    def __init__(self, live, C, ops, ops_ptr):
+        self._at = {e: k for k, e in enumerate(live)}
+        self._C, self._ops, self._ptr, self._made = C, ops, ops_ptr, {}
+
+    def __contains__(self, e):
+        return e in self._at
+
+    def __getitem__(self, e):
+        hit = self._made.get(e)
+        if hit is None:
+            k, (c_acc, t_acc) = self._at[e], e
+            p = self._ptr[2 * k:2 * k + 3].tolist()
+            hit = self._made[e] = (SWM._ops_to_alignment(self._ops[p[0]:p[1]].tolist(), self._C[t_acc], self._C[c_acc]),
+                                   SWM._ops_to_alignment(self._ops[p[1]:p[2]].tolist(), self._C[c_acc], self._C[t_acc]))
+            EDGE_VARIANT_STATS["lazy_expansions"] += 1
+        return hit
+
+
+def _file_variant_records(rows):
+    """(variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c) from an edge's variant records in column order, each
+    (i, key on t, key on c, u_v, type, p_t, p_c, snippet of aln_c, snippet of aln_t): filing every record under its keys in that order is
+    the reference's loop (functions.get_variant_coordinates) -- a later variant on the same key overwrites the entry and keeps the key's place"""
+    variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c = [], {}, {}, {}, {}
+    for i, key_t, key_c, u_v, v_type, p_t, p_c, snip_c, snip_t in rows:
+        variants.append((i, p_t, p_c))
+        entry = (v_type, p_c, u_v)
+        variant_coords_t[key_t] = entry
+        variant_coords_c[key_c] = entry
+        alignment_c_to_t[key_t] = snip_c
+        alignment_t_to_c[key_c] = snip_t
+    return variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c
+
+
+def _edge_variant_capacities(ops, ops_ptr):
+    """record slots an edge needs at most: the larger of its two lists' columns of ops other than '=' (ops_ptr: 2 n + 1 offsets into ops)"""
+    ops = np.asarray(ops, dtype=np.uint32)
+    ptr = np.asarray(ops_ptr, dtype=np.int64)
+    cols = np.where((ops & 15) != 0, ops >> 4, 0).astype(np.int64)
+    before = np.zeros(len(cols) + 1, dtype=np.int64)
+    np.cumsum(cols, out=before[1:])
+    per_list = before[ptr[1:]] - before[ptr[:-1]]
+    return np.maximum(per_list[0::2], per_list[1::2])
+
+
+def _edge_variants_call(seqs, edge_t, edge_c, ops, ops_ptr, rec_ptr=None):
+    """one isocon_edge_variants call on plain arrays (seqs: the sequences as str; ops_ptr: 2 n + 1 offsets into ops): (flipped, n_var, bad,
+    records (slots, 8) int32, snip_ptr, snippets of aln_c as str, snippets of aln_t as str, rec_ptr)"""
+    n = len(edge_t)
+    ops = np.ascontiguousarray(ops, dtype=np.uint32)
+    ops_ptr = np.ascontiguousarray(ops_ptr, dtype=np.uint64)
+    if rec_ptr is None:
+        rec_ptr = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(_edge_variant_capacities(ops, ops_ptr), out=rec_ptr[1:])
+    rec_ptr = np.ascontiguousarray(rec_ptr, dtype=np.uint64)
+    seq_ptr = np.zeros(len(seqs) + 1, dtype=np.uint64)
+    np.cumsum(np.fromiter((len(x) for x in seqs), dtype=np.uint64, count=len(seqs)), out=seq_ptr[1:])
+    seq_bytes = np.frombuffer("".join(seqs).encode("ascii"), dtype=np.uint8)
+    if len(seq_bytes) == 0:
+        seq_bytes = np.zeros(1, dtype=np.uint8)
+    edge_t = np.ascontiguousarray(edge_t, dtype=np.uint32)
+    edge_c = np.ascontiguousarray(edge_c, dtype=np.uint32)
+    n_slots = int(rec_ptr[n] - rec_ptr[0]) if n else 0
+    flipped, bad, n_var = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint32)
+    recs = np.zeros((max(n_slots, 1), 8), dtype=np.int32)
+    snip_ptr = np.zeros(n_slots + 1, dtype=np.uint64)
+    cap = 8 * n_slots + 64          # (a snippet is u_v + 2 columns; a too-small guess means running the call again)
+    needed, ms = ctypes.c_uint64(0), ctypes.c_float(0.0)
+    while True:
+        snip_c, snip_t = np.zeros(cap, dtype=np.uint8), np.zeros(cap, dtype=np.uint8)
+        rc = _lib.lib().isocon_edge_variants(_ptr(seq_bytes, _lib.u8p), _ptr(seq_ptr, _lib.u64p), len(seqs), n, _ptr(edge_t, _lib.u32p), _ptr(edge_c, _lib.u32p),
+                                             _ptr(ops if len(ops) else np.zeros(1, dtype=np.uint32), _lib.u32p), _ptr(ops_ptr, _lib.u64p), _ptr(rec_ptr, _lib.u64p),
+                                             _ptr(flipped, _lib.u8p), _ptr(n_var, _lib.u32p), _ptr(bad, _lib.u8p), _ptr(recs, _lib.i32p), _ptr(snip_ptr, _lib.u64p),
+                                             _ptr(snip_c, _lib.u8p), _ptr(snip_t, _lib.u8p), cap, ctypes.byref(needed), ctypes.byref(ms))
+        EDGE_VARIANT_STATS["kernel_ms"] += ms.value
+        if rc == _lib.ISOCON_E_CAPACITY:
+            cap = int(needed.value) + 64
+            continue
+        _lib.check(rc, "isocon_edge_variants")
+        break
+    EDGE_VARIANT_STATS["calls"] += 1          # (a call repeated with larger snippet buffers counts once)
+    EDGE_VARIANT_STATS["edges"] += n
+    total = int(snip_ptr[n_slots])
+    return (flipped[:n], n_var[:n], bad[:n], recs[:n_slots], snip_ptr.astype(np.int64), snip_c[:total].tobytes().decode("ascii"), snip_t[:total].tobytes().decode("ascii"),
+            rec_ptr.astype(np.int64))
+
+
+def _tuples_from_edge_records(n, n_var, recs, snip_ptr, snip_c, snip_t, rec_ptr):
+    """the tuple of _edge_variants for every edge of an isocon_edge_variants answer"""
+    R = recs.tolist()
+    sp = snip_ptr.tolist()
+    first = (rec_ptr - rec_ptr[0]).tolist() if n else [0]
+    counts = n_var.tolist()
+    out = []
+    for e in range(n):
+        rows = []
+        for s in range(first[e], first[e] + counts[e]):
+            i, _, _, key_t, key_c, u_v, _, packed = R[s]
+            rows.append((i, key_t, key_c, u_v, chr(packed & 255), chr(packed >> 8 & 255), chr(packed >> 16 & 255), snip_c[sp[s]:sp[s + 1]], snip_t[sp[s]:sp[s + 1]]))
+        out.append(_file_variant_records(rows))
+    return out
+
+
+def _edge_variants_on_device(live, C, ops, ops_ptr):
+    """[_edge_variants(t, c, alignment (t, c), alignment (c, t))] for the edges (c_acc, t_acc) of `live` from the alignments' ops -- list 2 k
+    = ops[ops_ptr[2 k]:ops_ptr[2 k + 1]] the (t, c) alignment of edge k, list 2 k + 1 the (c, t) one -- without the gapped strings:
+    isocon_edge_variants, one call per EDGE_VARIANT_BATCH edges.  Equal under == and in the dicts' key order."""
+    ops = np.ascontiguousarray(ops, dtype=np.uint32)
+    ops_ptr = np.asarray(ops_ptr, dtype=np.int64)
+    out = []
+    for lo in range(0, len(live), EDGE_VARIANT_BATCH):
+        part = live[lo:lo + EDGE_VARIANT_BATCH]
+        index, seqs = {}, []
+        for e in part:
+            for acc in e:
+                if acc not in index:
+                    index[acc] = len(seqs)
+                    seqs.append(C[acc])
+        edge_c = [index[c_acc] for c_acc, _ in part]
+        edge_t = [index[t_acc] for _, t_acc in part]
+        ptr = ops_ptr[2 * lo:2 * (lo + len(part)) + 1]
+        flipped, n_var, bad, recs, snip_ptr, snip_c, snip_t, rec_ptr = _edge_variants_call(seqs, edge_t, edge_c, ops[int(ptr[0]):int(ptr[-1])], ptr - ptr[0])
+        if bad.any():
+            raise RuntimeError("isocon_edge_variants: the ops of edge %r do not spell its two sequences" % (part[int(np.flatnonzero(bad)[0])],))
+        out.extend(_tuples_from_edge_records(len(part), n_var, recs, snip_ptr, snip_c, snip_t, rec_ptr))
+    return out
 
 
 def _edge_variants(t_seq, c_seq, alignment_tc, alignment_ct):
@@ -710,12 +855,19 @@ def do_statistical_tests_per_edge(nearest_neighbor_graph, C, X, read_partition, 
     for c, t in live:
         pairs.append((C[t], C[c]))
         pairs.append((C[c], C[t]))
-    alignments = SWM._align_pairs(pairs, [-3] * len(pairs), 2, 3, 1) if pairs else []
-    of_edge = {e: (alignments[2 * i], alignments[2 * i + 1]) for i, e in enumerate(live)}
     p_values = {c_acc: {} for c_acc in nearest_neighbor_graph}
     on_device = device_tables_enabled()
+    if on_device and pairs and edge_variants_on_device_enabled():
+        # the alignments stay ops: variants, coordinates and snippets of all edges from the device, gapped strings only on demand
+        ops, ops_ptr = SWM._align_pairs(pairs, [-3] * len(pairs), 2, 3, 1, want_ops=True)
+        of_edge = _LazyAlignments(live, C, ops, ops_ptr)
+        variants_of = dict(zip(live, _edge_variants_on_device(live, C, ops, ops_ptr)))
+    else:
+        alignments = SWM._align_pairs(pairs, [-3] * len(pairs), 2, 3, 1) if pairs else []
+        of_edge = {e: (alignments[2 * i], alignments[2 * i + 1]) for i, e in enumerate(live)}
+        variants_of = None
     if on_device:
-        done = _tests_on_device(live, of_edge, C, read_partition, ccs_dict, getattr(params, "max_phred_q_trusted", None))
+        done = _tests_on_device(live, of_edge, C, read_partition, ccs_dict, getattr(params, "max_phred_q_trusted", None), variants_of)
     else:
         tables = _tables_for([(C[acc], read_partition[acc]) for e in live for acc in e])
     for c_acc, t_acc in edges:
@@ -723,13 +875,13 @@ def do_statistical_tests_per_edge(nearest_neighbor_graph, C, X, read_partition, 
             p_values[c_acc][t_acc] = (1.0, 1.0, 0, 0, "")
             continue
         assert not (set(read_partition[c_acc]) & set(read_partition[t_acc]))
-        tc, ct = of_edge[(c_acc, t_acc)]
         if ccs_dict:
             for x_acc in read_partition[c_acc]:
                 assert X[x_acc] == ccs_dict[x_acc].seq
         if on_device:
             delta_t, p_value, n_support, used = done[(c_acc, t_acc)]
         else:
+            tc, ct = of_edge[(c_acc, t_acc)]
             delta_t, p_value, n_support, used = _test_on_tables(C[t_acc], C[c_acc], tc, ct, tables[id(read_partition[c_acc])],
                                                                 tables[id(read_partition[t_acc])], ccs_dict, getattr(params, "max_phred_q_trusted", None))
         p_values[c_acc][t_acc] = _result(c_acc, t_acc, C[t_acc], delta_t, p_value, range(n_support), used, bool(ccs_dict))[2:]

@@ -40,4 +40,7 @@ with tempfile.TemporaryDirectory() as tmp:
     rounds = len([f for f in os.listdir(tmp) if f.startswith("p_values_")])
     print("stat_filter_candidates: %.1f s, %d rounds -> %d final candidates (%d are true isoforms of %d)" % (t2, rounds, len(C), len(set(C.values()) & set(isoforms)), len(isoforms)), flush=True)
     print("whole pipeline: %.1f s for %d reads x ~%d bp" % (t1 + t2, n, L))
+    from isocon_amd import hypothesis_test_module as H
+    print("device read tables: %s" % H.DEVICE_STATS)
+    print("edge variants on the device (isocon_edge_variants; none under ISOCON_DEBUG_VARIANT=stat_host_variants): %s" % H.EDGE_VARIANT_STATS, flush=True)
     pstats.Stats(pr).sort_stats("cumulative").print_stats(28)
