@@ -289,6 +289,7 @@ int isocon_exon_filter_from_ops(const uint32_t *ops, const uint64_t *ops_ptr, ui
  * smallest is replaced by the majority.  Output: the corrected rows without their '-' symbols, packed
  * (out_offsets[n_rows + 1]), out_n_cand[r] = number of correctable positions (rows with more than the 2048 the kernel
  * keeps in LDS are run again with their list in HBM), out_class_totals[3] = insertion, deletion, substitution totals.
+ * The matrix is handled as a batch of one partition by the kernels of the batched entry points below (csrc/msa.hpp).
  * ISOCON_E_CAPACITY if packed_cap is too small (out_offsets[n_rows] holds the size needed). */
 int isocon_msa_correct(const uint8_t *matrix, uint32_t n_rows, uint32_t n_cols, const int32_t *degree,
                        uint8_t *out_packed, uint64_t packed_cap, uint64_t *out_offsets, int32_t *out_n_cand,
@@ -312,6 +313,10 @@ int isocon_msa_correct(const uint8_t *matrix, uint32_t n_rows, uint32_t n_cols, 
  *   isocon_msa_correct_built  patches (patch_bytes[patch_ptr[i] .. patch_ptr[i + 1]) into row patch_row[i] from column patch_col[i]),
  *                             then isocon_msa_correct on the built matrix (same outputs).  One build serves one correction.
  *   isocon_msa_read_built     the built matrix (tests).
+ * These are the batched entry points below on a batch of one partition (same kernels; word 6 of a wide record, the partition, is 0).  A
+ * build pairs only with the correction of its own kind: isocon_msa_correct_built / isocon_msa_read_built after isocon_msa_build_ops_batch
+ * is ISOCON_E_ARG, and so is isocon_msa_correct_built_batch after isocon_msa_build_ops.  isocon_msa_correct on the process' scratch pool
+ * uses the slots of a build in that pool: such a build is no longer there afterwards.
  */
 int isocon_msa_build_ops(isocon_store *s, uint32_t n_rows, const uint32_t *row_ids, const uint32_t *ops, const uint64_t *ops_ptr,
                          uint32_t *out_n_cols, uint32_t *out_col_slot, uint32_t *out_longest, uint32_t *out_wide, uint64_t wide_cap,
@@ -329,7 +334,8 @@ int isocon_msa_read_built(isocon_store *s, uint32_t n_rows, uint32_t n_cols, uin
  * index the concatenation, the slot arrays (out_col_slot, out_longest) are concatenated too (len(centre) + 1 entries per partition, in
  * partition order).  Wide records as in isocon_msa_build_ops with the row as an index into the concatenation and the partition in word 6;
  * patches address (row of the concatenation, column of that row's matrix).  out_n_cand[r] = -1 for a row with more correctable positions
- * than the kernel keeps in LDS: its partition has to be corrected through the single-partition entry points (its output rows are not valid).
+ * than the 1024 the kernel keeps in LDS in this call: its partition has to be corrected through the single-partition entry points (its output
+ * rows are not valid).  If packed_cap is too small (ISOCON_E_CAPACITY, out_offsets[n_rows] holds the size needed) the build stays: call again.
  */
 int isocon_msa_build_ops_batch(isocon_store *s, uint32_t n_parts, const uint32_t *first_row, const uint32_t *row_ids, const uint32_t *ops,
                                const uint64_t *ops_ptr, uint32_t *out_n_cols, uint32_t *out_col_slot, uint32_t *out_longest, uint32_t *out_wide,

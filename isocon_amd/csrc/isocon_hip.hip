@@ -23,8 +23,6 @@
 #include "partition_host.hpp"
 #include "sg.hpp"
 #include "msa.hpp"
-#include "msa_build.hpp"
-#include "msa_batch.hpp"
 #include "hw.hpp"
 #include "hw_tiles.hpp"
 #include "hw_full.hpp"
@@ -81,11 +79,11 @@ struct BoundTag {
     int32_t kcap = 0;
     unsigned long long lb_total = 0;
 };
-// MsaTag: the multi-alignment matrix isocon_msa_build_ops left in SLOT_MSA_IN for isocon_msa_correct_built.
-struct MsaTag { bool valid = false; uint64_t serial = 0; uint32_t n_rows = 0, n_cols = 0; };
-// MsaBatchHost: the matrices isocon_msa_build_ops_batch left on the device for isocon_msa_correct_built_batch, with the host's copy of their layout.
-struct MsaBatchHost {
-    bool valid = false;
+// MsaBuilt: the matrices a build left in SLOT_MSA_IN (their partition tables in SLOT_MSA_PART .. SLOT_MSA_CBASE) for the correction that
+// follows, with the host's copy of their layout.  `by`: which entry point built them -- isocon_msa_correct_built / isocon_msa_read_built pair
+// with isocon_msa_build_ops only, isocon_msa_correct_built_batch with isocon_msa_build_ops_batch only.
+struct MsaBuilt {
+    enum By { NONE, SINGLE, BATCH } by = NONE;
     uint64_t serial = 0;
     uint32_t n_parts = 0, n_rows = 0;
     std::vector<uint32_t> ncols, col_base, first_row;
@@ -101,8 +99,7 @@ struct ScratchPool {
     Slot slots[160];
     BoundTag bound_tag;
     HeldHits held_hits;
-    MsaTag msa_tag;
-    MsaBatchHost msab;
+    MsaBuilt msa;
     void *get(int idx, size_t bytes)
     {
         Slot &s = slots[idx];
@@ -122,8 +119,7 @@ struct ScratchPool {
         for (Slot &s : slots) { if (s.p) (void)hipFree(s.p); s.p = nullptr; s.cap = 0; }
         bound_tag = BoundTag();
         held_hits = HeldHits();
-        msa_tag = MsaTag();
-        msab = MsaBatchHost();
+        msa = MsaBuilt();
     }
 };
 
@@ -132,7 +128,7 @@ enum {
     SLOT_NN_BEST, SLOT_NN_QF, SLOT_NN_TF, SLOT_NN_HITS, SLOT_NN_HITCOUNT, SLOT_NN_STATS, SLOT_NN_TS, SLOT_NN_IDS, SLOT_NN_PLANES2, SLOT_NN_PERM, SLOT_NN_IL, SLOT_NN_IL2, SLOT_NN_HITS2, SLOT_NN_HITCOUNT2, SLOT_NN_QPROF, SLOT_NN_QSUM, SLOT_NN_LB, SLOT_NN_LBROW, SLOT_NN_LBLEN, SLOT_NN_SLOTORDER, SLOT_NN_LBCHUNKS, SLOT_NN_ROWMIN, SLOT_NN_COLMIN, SLOT_NN_SEED_A, SLOT_NN_SEED_B, SLOT_NN_SEED_N, SLOT_NN_LBT, SLOT_NN_LBT_OFF, SLOT_NN_LBT_SLO, SLOT_NN_LBT_LEN, SLOT_NN_LBT_PAD, SLOT_NN_SCORE, SLOT_NN_LDEST, SLOT_NN_FIN_HITS, SLOT_NN_FIN_CNT, SLOT_NN_FIN_START, SLOT_NN_FIN_CUR, SLOT_NN_FIN_NB, SLOT_NN_FIN_LEN2, SLOT_NN_FIN_ROWPTR, SLOT_NN_FIN_COLS, SLOT_NN_FIN_FLAG, SLOT_NN_FIN_BEST, SLOT_NN_ACC_HITS, SLOT_NN_LTOT, SLOT_NN_LCHUNKS, SLOT_NN_LIST, SLOT_NN_LPA, SLOT_NN_LPB, SLOT_NN_TEXT2, SLOT_NN_LTASKS,
     SLOT_NN2_STATE, SLOT_NN2_TPOS, SLOT_NN2_EXC, SLOT_NN2_CTR, SLOT_NN2_PAIRS, SLOT_NN2_WIDE,
     SLOT_SG_PAIRS, SLOT_SG_R, SLOT_SG_TRACE, SLOT_SG_END, SLOT_SG_OPS, SLOT_SG_CNT, SLOT_SG_RES, SLOT_SG_OFF, SLOT_SG_DENSE, SLOT_SG_BOUND, SLOT_SG_AOFF, SLOT_SG_ALNA, SLOT_SG_ALNB,
-    SLOT_MSA_IN, SLOT_MSA_OUT, SLOT_MSA_DEG, SLOT_MSA_COUNTS, SLOT_MSA_MAJ, SLOT_MSA_FLAGS, SLOT_MSA_TOT, SLOT_MSA_NCAND, SLOT_MSA_LEN, SLOT_MSA_OFF, SLOT_MSA_PACKED, SLOT_MSA_ROWS, SLOT_MSA_OPS, SLOT_MSA_OPTR, SLOT_MSA_LONGEST, SLOT_MSA_WIDTH, SLOT_MSA_CSLOT, SLOT_MSA_LTOT, SLOT_MSA_WIDE, SLOT_MSA_PROW, SLOT_MSA_PCOL, SLOT_MSA_PPTR, SLOT_MSA_PBYTES, SLOT_MSAB_PART, SLOT_MSAB_FIRST, SLOT_MSAB_LM, SLOT_MSAB_SBASE, SLOT_MSAB_NCOLS, SLOT_MSAB_MOFF, SLOT_MSAB_CBASE, SLOT_MSAB_CBP, SLOT_MSAB_CBC, SLOT_MSAB_CBR,
+    SLOT_MSA_IN, SLOT_MSA_OUT, SLOT_MSA_DEG, SLOT_MSA_COUNTS, SLOT_MSA_MAJ, SLOT_MSA_FLAGS, SLOT_MSA_TOT, SLOT_MSA_NCAND, SLOT_MSA_LEN, SLOT_MSA_OFF, SLOT_MSA_PACKED, SLOT_MSA_ROWS, SLOT_MSA_OPS, SLOT_MSA_OPTR, SLOT_MSA_LONGEST, SLOT_MSA_WIDTH, SLOT_MSA_CSLOT, SLOT_MSA_LTOT, SLOT_MSA_WIDE, SLOT_MSA_PROW, SLOT_MSA_PCOL, SLOT_MSA_PPTR, SLOT_MSA_PBYTES, SLOT_MSA_PART, SLOT_MSA_FIRST, SLOT_MSA_LM, SLOT_MSA_SBASE, SLOT_MSA_NCOLS, SLOT_MSA_MOFF, SLOT_MSA_CBASE, SLOT_MSA_CBP, SLOT_MSA_CBC, SLOT_MSA_CBR,
     SLOT_HW_Q, SLOT_HW_T, SLOT_HW_K, SLOT_HW_OUT, SLOT_HW_TRACE, SLOT_HW_CTR, SLOT_HW_TILEQ, SLOT_HW_LANES, SLOT_HW_PQ, SLOT_HW_KEY, SLOT_HW_HIST, SLOT_HW_CURSOR, SLOT_HW_TBASE, SLOT_HW_CLS,
     SLOT_PACK_ASCII, SLOT_PACK_OFF, SLOT_PACK_BAD, SLOT_PACK_HIST, SLOT_PACK_FLAGS, SLOT_EB_A, SLOT_EB_B, SLOT_EB_K, SLOT_EB_OUT, SLOT_EB_ROWS, SLOT_SCAN_TMP, SLOT_SCAN_SUMS,
     SLOT_RT_REF, SLOT_RT_IN, SLOT_RT_OUT,

@@ -1,24 +1,284 @@
-// msa.hpp -- consensus correction on a partition's multi-alignment matrix.
+// msa.hpp -- consensus correction of the partitions of a correction step (SURVEY.md 8(f) rows f1 + f3): their multi-alignment matrices built
+// ON THE DEVICE from the CIGAR ops of the (centre, member) alignments and the packed store, then column statistics, per-read correction and
+// gap stripping.  One kernel per step, all of them on a batch of partitions (MsaBatch); a single partition is a batch of one.
 //
-// Device part of /root/reference/modules/correction_module.py:260-446 once the matrix exists (the matrix itself -- with the
-// reference's insertion-slot layout -- is assembled on the host, isocon_amd/functions.py:msa_matrix):
-//   k_msa_col_stats  : per column the weighted counts of A, C, G, T, '-' (position frequency matrix, functions.py:526-536),
-//                      the majority symbol (first maximum in that order), whether it is unique, and the partition's totals
-//                      of the three error classes over the unambiguous columns (correction_module.py:296-307);
-//   k_msa_row_correct: one wavefront per read: its correctable positions (unambiguous majority differs), their frequency
-//                      own_count / class_total in double precision, the ceil(n/2)-th smallest frequency, and the
-//                      replacement of every position at or below it by the majority symbol (:329-402);
+// The matrix is what the reference's modules/functions.py:543-588 (create_multialignment_matrix), :598-631 (position_query_to_alignment)
+// and :679-767 (create_multialignment_format_NEW) assemble from the gapped strings of sw_align_sequences.  The gapped strings never exist
+// here: an alignment is its run-length ops (isocon_sg_trace_batch; ~50 per pair at 2.5 kb), the bases come from the store's bit-planes.
+// Layout (the reference's): in front of every centre base t and behind the last one sits a slot of insertion columns -- 1 column, or
+// longest + 2 where some member inserts 2 or more characters (functions.py:722-731) -- followed by the base column of t.
+//   k_msa_ops_scan     one thread per row: walks the row's ops, atomicMax of the insertion length per slot;
+//   k_msa_layout       one workgroup per partition: slot widths and the exclusive prefix sums that give every slot's first column;
+//   k_msa_fill         one wave per row: writes the row (the matrix is pre-filled with '-'); single-character insertions go to their
+//                      slot's column, the insertions of WIDE slots are only listed (row, slot, position in the member, length, first bases,
+//                      partition): where they sit inside the padded longest insertion is decided by get_best_solution (functions.py:635-676,
+//                      string heuristics with an alignment tie), which stays on the host and comes back as patches (k_msa_patch).
+// ops: len << 4 | code, code 0 '=', 1 'X', 2 'I' (centre base against a gap of the member), 3 'D' (member bases the centre lacks:
+// an insertion into the slot in front of the next centre base); the centre is the QUERY of its alignments (isocon_get_candidates.py:47).
+//
+// The correction is the reference's modules/correction_module.py:260-446 on those matrices:
+//   k_msa_col_counts / k_msa_col_finish: per column the weighted counts of A, C, G, T, '-' (position frequency matrix, functions.py:526-536),
+//                      the majority symbol (first maximum in that order), whether it is unique, and the partition's totals of the three
+//                      error classes over the unambiguous columns (correction_module.py:296-307);
+//   k_msa_row_correct  one wavefront per read: its correctable positions (unambiguous majority differs), their frequency
+//                      own_count / class_total in double precision, the ceil(n/2)-th smallest frequency, and the replacement of every
+//                      position at or below it by the majority symbol (:329-402);
 //   k_msa_row_lengths / k_msa_strip: the corrected rows without their gap symbols, packed.
 // Byte-matrix work, HBM-bound: the matrix is read three times and written once.
+//
+// Why a batch: the reference's correct_strings (correction_module.py:12-75) loops over the partitions (a Pool task each); later
+// correction steps of a run have hundreds to thousands of small partitions, and one build + correct call pair per partition is ~20 host
+// synchronisations each (2 751 call pairs over the ten steps of the 50 000-read set: 1.3 s).  So a row knows its partition (part_of_row)
+// and a partition its pieces of the concatenated arrays: slots (insertion-slot arrays, len(centre) + 1 entries), columns (ncols entries)
+// and matrix cells.
 #pragma once
 #include "common.hpp"
 
 namespace isocon {
 
-static constexpr int MSA_MAX_CAND = 2048;      // correctable positions per read held in LDS (more: the row is run again with
-                                               // its list in a global scratch row, k_msa_row_correct<true>)
+struct MsaBatch {
+    const uint32_t *part_of_row;          // [n_rows]
+    const uint32_t *first_row;            // [n_parts + 1]: rows of partition p = first_row[p] .. first_row[p + 1]; the first is its centre
+    const uint32_t *Lm;                   // [n_parts] length of the centre
+    const uint32_t *slot_base;            // [n_parts + 1] offset of the partition's slot arrays (longest, width, col_slot)
+    const uint32_t *ncols;                // [n_parts] columns of the partition's matrix (after k_msa_layout)
+    const unsigned long long *m_off;      // [n_parts + 1] first cell of the partition's matrix
+    const uint32_t *col_base;             // [n_parts + 1] offset of the partition's column arrays (counts, maj, flags)
+    uint32_t n_parts, n_rows;
+};
 
-// scratch accessors: LDS directly; global scratch through device-scope atomics (lanes read what other lanes of the wave wrote)
+__device__ __forceinline__ uint8_t msa_base_char(const DevStore &S, uint32_t id, uint32_t pos)
+{
+    const size_t w = ((size_t)(pos >> 6) * S.n + id) * 2;
+    const uint32_t sh = pos & 63u;
+    const uint32_t code = (uint32_t)((S.planes[w] >> sh) & 1ull) | ((uint32_t)((S.planes[w + 1] >> sh) & 1ull) << 1);
+    return (uint8_t)("ACGT"[code]);
+}
+
+__device__ __forceinline__ int msa_sym(uint8_t c)      // A C G T - -> 0..4
+{
+    return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4;
+}
+
+// longest[slot_base[p] + t] = longest insertion any row of partition p has in slot t (t = 0 .. Lm); bad[0] != 0 if a row's ops do not spell
+// the centre / the member
+__global__ __launch_bounds__(256) void k_msa_ops_scan(DevStore S, MsaBatch B, const uint32_t *__restrict__ row_ids, const uint32_t *__restrict__ ops,
+                                                       const unsigned long long *__restrict__ ops_ptr, uint32_t *__restrict__ longest, uint32_t *__restrict__ bad)
+{
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= B.n_rows) return;
+    const uint32_t p = B.part_of_row[r];
+    if (r == B.first_row[p]) return;          // the centre itself: no ops, no insertions
+    const uint32_t Lm = B.Lm[p];
+    uint32_t *lg = longest + B.slot_base[p];
+    uint32_t t = 0, sp = 0;
+    for (unsigned long long k = ops_ptr[r]; k < ops_ptr[r + 1]; ++k) {
+        const uint32_t op = ops[k], len = op >> 4, code = op & 15u;
+        if (code == 3u) { if (t <= Lm) atomicMax(lg + t, len); sp += len; }
+        else { t += len; if (code != 2u) sp += len; }
+    }
+    if (t != Lm || sp != (uint32_t)S.lens[row_ids[r]]) atomicOr(bad, 1u);
+}
+
+// width[t] = 1 or longest + 2; col_slot[t] = first column of slot t (the base column of t follows the slot); ncols_out[p] = the partition's
+// columns.  One workgroup of 1024 threads per partition.
+__global__ __launch_bounds__(1024) void k_msa_layout(MsaBatch B, const uint32_t *__restrict__ longest, uint32_t *__restrict__ width, uint32_t *__restrict__ col_slot,
+                                                      uint32_t *__restrict__ ncols_out)
+{
+    __shared__ unsigned long long wave_sums[16];
+    __shared__ unsigned long long carry;
+    const uint32_t p = blockIdx.x;
+    const uint32_t Lm = B.Lm[p], sb = B.slot_base[p];
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    for (uint32_t base = 0; base <= Lm; base += 1024u) {
+        const uint32_t t = base + threadIdx.x;
+        uint32_t w = 0;
+        if (t <= Lm) {
+            const uint32_t lg = longest[sb + t];
+            w = lg > 1u ? lg + 2u : 1u;
+            width[sb + t] = w;
+        }
+        unsigned long long total = 0;
+        const unsigned long long step = t <= Lm ? (unsigned long long)w + (t < Lm ? 1ull : 0ull) : 0ull;      // slot + its base column (the last slot has none)
+        const unsigned long long off = block_exscan_1024(step, wave_sums, &total);
+        if (t <= Lm) col_slot[sb + t] = (uint32_t)(carry + off);
+        __syncthreads();
+        if (threadIdx.x == 0) carry += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) ncols_out[p] = (uint32_t)carry;
+}
+
+// One wave per row.  wide[8 i ..] = row (of the concatenation), slot, first position in the member, length, the 2-bit codes (A C G T = 0 1 2 3)
+// of its first 32 bases (base j at bits 2 j of the 64-bit word lo | hi << 32), the partition, a spare word; wide_count: entries appended (may
+// exceed wide_cap: the host then calls again with room).
+__global__ __launch_bounds__(256) void k_msa_fill(DevStore S, MsaBatch B, const uint32_t *__restrict__ row_ids, const uint32_t *__restrict__ ops,
+                                                   const unsigned long long *__restrict__ ops_ptr, const uint32_t *__restrict__ longest_all,
+                                                   const uint32_t *__restrict__ width_all, const uint32_t *__restrict__ col_slot_all, uint8_t *__restrict__ M_all,
+                                                   uint32_t *__restrict__ wide, unsigned long long wide_cap, unsigned long long *__restrict__ wide_count)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t r = blockIdx.x * 4u + (uint32_t)wave;
+    if (r >= B.n_rows) return;
+    const uint32_t p = B.part_of_row[r], r0 = B.first_row[p], Lm = B.Lm[p], sb = B.slot_base[p], n_cols = B.ncols[p];
+    const uint32_t *longest = longest_all + sb, *width = width_all + sb, *col_slot = col_slot_all + sb;
+    const uint32_t id = row_ids[r];
+    uint8_t *row = M_all + B.m_off[p] + (size_t)(r - r0) * n_cols;
+    if (r == r0) {          // the centre: its own bases in the base columns
+        for (uint32_t t = (uint32_t)lane; t < Lm; t += 64u) row[col_slot[t] + width[t]] = msa_base_char(S, id, t);
+        return;
+    }
+    // The row's ops, 64 at a time: every lane loads one (coalesced), a wave scan gives each op its slot and member position, and the ops are then
+    // taken one by one from the lanes' registers -- no chain of dependent global loads (op k + 1 could not be requested before op k had arrived).
+    uint32_t t = 0, sp = 0;
+    const unsigned long long k_end = ops_ptr[r + 1];
+    for (unsigned long long kb = ops_ptr[r]; kb < k_end; kb += 64ull) {
+        const uint32_t n_here = (uint32_t)(k_end - kb < 64ull ? k_end - kb : 64ull);
+        const uint32_t op_l = (uint32_t)lane < n_here ? ops[kb + (unsigned long long)lane] : 0u;
+        const uint32_t len_l = op_l >> 4, code_l = op_l & 15u;
+        uint32_t it = code_l == 3u ? 0u : len_l, is = code_l == 2u ? 0u : len_l;          // inclusive scans of the advances in slot / member position
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t ot = (uint32_t)__shfl_up((int)it, d, 64), os = (uint32_t)__shfl_up((int)is, d, 64);
+            if (lane >= d) { it += ot; is += os; }
+        }
+        const uint32_t t_l = t + it - (code_l == 3u ? 0u : len_l), sp_l = sp + is - (code_l == 2u ? 0u : len_l);
+        // Insertions at wide slots are only LISTED (their place inside the padded longest insertion is decided on the host): every lane files
+        // its own op's record, ONE atomic per batch reserves the records (one atomic per record -- 6 10^5 on one address at C3 -- was what the
+        // kernel's 3.7 ms were: same-address atomics serialise in L2).
+        {
+            // (a malformed op stream -- an op that runs past the member row -- ends the row at that op below: the records of the ops behind it
+            // are not listed either: the lanes in front of the first op that fails the bound)
+            const unsigned long long bad = __ballot((uint32_t)lane < n_here && t_l + (code_l == 3u ? 0u : len_l) > Lm);
+            const bool before_bad = bad == 0ull || (uint32_t)lane < (uint32_t)__builtin_ctzll(bad);
+            const bool wide_l = before_bad && (uint32_t)lane < n_here && code_l == 3u && t_l <= Lm && longest[t_l] > 1u;
+            const unsigned long long wm = __ballot(wide_l);
+            if (wm != 0ull) {
+                unsigned long long at0 = 0;
+                if (lane == 0) at0 = atomicAdd(wide_count, (unsigned long long)__popcll(wm));
+                at0 = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(at0 >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)at0);
+                const unsigned long long at = at0 + (unsigned long long)__popcll(wm & (((unsigned long long)1 << lane) - 1ull));
+                if (wide_l && at < wide_cap) {
+                    unsigned long long codes = 0;
+                    for (uint32_t jj = 0; jj < len_l && jj < 32u; ++jj) {
+                        const size_t w = ((size_t)((sp_l + jj) >> 6) * S.n + id) * 2;
+                        const uint32_t sh = (sp_l + jj) & 63u;
+                        codes |= (((S.planes[w] >> sh) & 1ull) | (((S.planes[w + 1] >> sh) & 1ull) << 1)) << (2u * jj);
+                    }
+                    uint32_t *e = wide + 8 * at;
+                    e[0] = r; e[1] = t_l; e[2] = sp_l; e[3] = len_l; e[4] = (uint32_t)codes; e[5] = (uint32_t)(codes >> 32); e[6] = p; e[7] = 0u;
+                }
+            }
+        }
+        for (uint32_t j = 0; j < n_here; ++j) {
+            const uint32_t op = (uint32_t)__builtin_amdgcn_readlane((int)op_l, (int)j), len = op >> 4, code = op & 15u;
+            const uint32_t tj = (uint32_t)__builtin_amdgcn_readlane((int)t_l, (int)j), spj = (uint32_t)__builtin_amdgcn_readlane((int)sp_l, (int)j);
+            if (tj + (code == 3u ? 0u : len) > Lm) return;          // (ops that do not spell the centre were reported by k_msa_ops_scan)
+            if (code == 3u) {
+                if (longest[tj] <= 1u && lane == 0) row[col_slot[tj]] = msa_base_char(S, id, spj);          // (wide slots: listed above)
+            } else {
+                for (uint32_t i = (uint32_t)lane; i < len; i += 64u)
+                    row[col_slot[tj + i] + width[tj + i]] = code == 2u ? (uint8_t)'-' : msa_base_char(S, id, spj + i);
+            }
+        }
+        t += (uint32_t)__shfl((int)it, 63, 64);
+        sp += (uint32_t)__shfl((int)is, 63, 64);
+    }
+}
+
+// patches: bytes[ptr[i] .. ptr[i + 1]) go to row patch_row[i] (of the concatenation) from column patch_col[i] of its matrix on (one wave per patch)
+__global__ __launch_bounds__(256) void k_msa_patch(uint8_t *__restrict__ M_all, MsaBatch B, const uint32_t *__restrict__ patch_row, const uint32_t *__restrict__ patch_col,
+                                                    const uint32_t *__restrict__ patch_ptr, const uint8_t *__restrict__ bytes, uint32_t n_patches)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t i = blockIdx.x * 4u + (uint32_t)wave;
+    if (i >= n_patches) return;
+    const uint32_t r = patch_row[i], p = B.part_of_row[r];
+    uint8_t *dst = M_all + B.m_off[p] + (size_t)(r - B.first_row[p]) * B.ncols[p] + patch_col[i];
+    const uint32_t b = patch_ptr[i], e = patch_ptr[i + 1];
+    for (uint32_t k = b + (uint32_t)lane; k < e; k += 64u) dst[k - b] = bytes[k];
+}
+
+// Column statistics in two launches (one thread per column walking ALL rows of its partition -- 11 000 at C3 -- took 6.2 ms with 110
+// workgroups on the chip):
+//   k_msa_col_counts   workgroup b = the 256 columns cbr[3b + 1] .. of partition cbr[3b], rows cbr[3b + 2] .. + MSA_ROWS_PER_WG (host-built table):
+//                      per-column symbol counts of that row chunk, weighted by the rows' degrees, added to counts (zeroed by the host);
+//                      counts[5 col_base[p] + s * ncols + col]
+//   k_msa_col_finish   workgroup b = the 256 columns cb_col0[b] .. of partition cb_part[b]: maj[col] = majority symbol index, flags[col] bit 0 =
+//                      unambiguous, class_tot[3 p ..] = the partition's error-class totals (ins, del, subs; zeroed by the host)
+static constexpr uint32_t MSA_ROWS_PER_WG = 256;
+
+__global__ __launch_bounds__(256) void k_msa_col_counts(const uint8_t *__restrict__ M_all, MsaBatch B, const uint32_t *__restrict__ cbr, const int32_t *__restrict__ degree,
+                                                         int32_t *__restrict__ counts_all)
+{
+    const uint32_t p = cbr[3 * blockIdx.x], col = cbr[3 * blockIdx.x + 1] + threadIdx.x, row0 = cbr[3 * blockIdx.x + 2];
+    const uint32_t ncols = B.ncols[p], r0 = B.first_row[p], nr = B.first_row[p + 1] - r0;
+    if (col >= ncols) return;
+    const uint32_t row1 = row0 + MSA_ROWS_PER_WG < nr ? row0 + MSA_ROWS_PER_WG : nr;
+    const uint8_t *M = M_all + B.m_off[p];
+    int32_t c[5] = {0, 0, 0, 0, 0};
+#pragma unroll 8
+    for (uint32_t r = row0; r < row1; ++r) {
+        const int sidx = msa_sym(M[(size_t)r * ncols + col]);
+        const int32_t d = degree[r0 + r];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) c[k] += sidx == k ? d : 0;
+    }
+    int32_t *counts = counts_all + (size_t)5 * B.col_base[p];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) if (c[k]) atomicAdd(counts + (size_t)k * ncols + col, c[k]);
+}
+
+__global__ __launch_bounds__(256) void k_msa_col_finish(MsaBatch B, const uint32_t *__restrict__ cb_part, const uint32_t *__restrict__ cb_col0,
+                                                         const int32_t *__restrict__ counts_all, uint8_t *__restrict__ maj_all,
+                                                         uint8_t *__restrict__ flags_all, unsigned long long *__restrict__ class_tot_all)
+{
+    const uint32_t p = cb_part[blockIdx.x], col = cb_col0[blockIdx.x] + threadIdx.x;
+    const uint32_t ncols = B.ncols[p];
+    const int32_t *counts = counts_all + (size_t)5 * B.col_base[p];
+    long long ci = 0, cd = 0, cs = 0;
+    if (col < ncols) {
+        int32_t c[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) c[k] = counts[(size_t)k * ncols + col];
+        int best = 0, ties = 1;
+#pragma unroll
+        for (int k = 1; k < 5; ++k) {
+            if (c[k] > c[best]) { best = k; ties = 1; }
+            else if (c[k] == c[best]) ++ties;
+        }
+        int32_t tot = 0;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) tot += c[k];
+        maj_all[B.col_base[p] + col] = (uint8_t)best;
+        flags_all[B.col_base[p] + col] = ties == 1 ? 1 : 0;
+        if (ties == 1) {
+            if (best == 4) ci = tot - c[4];
+            else { cd = c[4]; cs = tot - c[best] - c[4]; }
+        }
+    }
+    // block reduction of the three totals
+    __shared__ long long red[3][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int o = 32; o > 0; o >>= 1) { ci += __shfl_xor(ci, o, 64); cd += __shfl_xor(cd, o, 64); cs += __shfl_xor(cs, o, 64); }
+    if (lane == 0) { red[0][wave] = ci; red[1][wave] = cd; red[2][wave] = cs; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const long long t = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+        if (t) atomicAdd(class_tot_all + (size_t)3 * p + threadIdx.x, (unsigned long long)t);
+    }
+}
+
+// Correctable positions per row that k_msa_row_correct<CAP> keeps in LDS.  2 048: a workgroup of four rows takes 96 KB -- ONE workgroup per CU,
+// one wave per SIMD, 4.2 ms for the 50 000 rows of C3 (25-60 candidates each).  1 024: 48 KB, three workgroups per CU; the batched entry point
+// runs that one and hands a row with more (reads of > 8 kb at ONT error rates) back to its caller, who sends the row's partition through the
+// single-partition entry points; those run 2 048 and then MSA_LIST_HBM for the rows that are left.
+static constexpr int MSA_BATCH_CAND = 1024;
+static constexpr int MSA_MAX_CAND = 2048;
+static constexpr int MSA_LIST_HBM = 0;          // as CAP: the list in a global scratch row, as long as the row's matrix is wide
+
+// list accessors: LDS directly; global scratch through device-scope atomics (lanes read what other lanes of the wave wrote)
 template <bool GLOBAL> __device__ __forceinline__ void msa_put(double *fq, uint32_t *cl, uint32_t at, double f, uint32_t col)
 {
     if (GLOBAL) {
@@ -37,80 +297,37 @@ template <bool GLOBAL> __device__ __forceinline__ uint32_t msa_col(const uint32_
     return cl[i];
 }
 
-__device__ __forceinline__ int msa_sym(uint8_t c)      // A C G T - -> 0..4
+// One wavefront per row.  out row = corrected row; n_cand[r] = number of correctable positions.  CAP > 0: every row of the batch, its list in
+// LDS; a row with more than CAP positions gets n_cand = -1 and is left to the caller.  CAP = MSA_LIST_HBM: the rows of `row_list` (n_list of
+// them), their lists in g_freq / g_col (list_stride entries per listed row: at least the widest of their matrices).
+template <int CAP>
+__global__ __launch_bounds__(256) void k_msa_row_correct(const uint8_t *__restrict__ M_all, uint8_t *__restrict__ out_all, MsaBatch B, const int32_t *__restrict__ degree,
+                                                          const int32_t *__restrict__ counts_all, const uint8_t *__restrict__ maj_all, const uint8_t *__restrict__ flags_all,
+                                                          const unsigned long long *__restrict__ class_tot_all, int32_t *__restrict__ n_cand,
+                                                          const uint32_t *__restrict__ row_list, uint32_t n_list, double *g_freq, uint32_t *g_col, uint32_t list_stride)
 {
-    return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4;
-}
-
-// counts[s * ncols + col]; maj[col] = majority symbol index; flags[col] bit 0 = unambiguous
-__global__ __launch_bounds__(256) void k_msa_col_stats(const uint8_t *__restrict__ M, uint32_t nr, uint32_t ncols, const int32_t *__restrict__ degree,
-                                                        int32_t *__restrict__ counts, uint8_t *__restrict__ maj, uint8_t *__restrict__ flags,
-                                                        unsigned long long *__restrict__ class_tot /* ins, del, subs */)
-{
-    const uint32_t col = blockIdx.x * 256 + threadIdx.x;
-    long long ci = 0, cd = 0, cs = 0;
-    if (col < ncols) {
-        int32_t c[5] = {0, 0, 0, 0, 0};
-        for (uint32_t r = 0; r < nr; ++r) {
-            const int sidx = msa_sym(M[(size_t)r * ncols + col]);
-            const int32_t d = degree[r];
-#pragma unroll
-            for (int k = 0; k < 5; ++k) c[k] += sidx == k ? d : 0;
-        }
-        int best = 0, ties = 1;
-#pragma unroll
-        for (int k = 1; k < 5; ++k) {
-            if (c[k] > c[best]) { best = k; ties = 1; }
-            else if (c[k] == c[best]) ++ties;
-        }
-        int32_t tot = 0;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) { counts[(size_t)k * ncols + col] = c[k]; tot += c[k]; }
-        maj[col] = (uint8_t)best;
-        flags[col] = ties == 1 ? 1 : 0;
-        if (ties == 1) {
-            if (best == 4) ci = tot - c[4];
-            else { cd = c[4]; cs = tot - c[best] - c[4]; }
-        }
-    }
-    // block reduction of the three totals
-    __shared__ long long red[3][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int o = 32; o > 0; o >>= 1) { ci += __shfl_xor(ci, o, 64); cd += __shfl_xor(cd, o, 64); cs += __shfl_xor(cs, o, 64); }
-    if (lane == 0) { red[0][wave] = ci; red[1][wave] = cd; red[2][wave] = cs; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const long long t = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
-        if (t) atomicAdd(class_tot + threadIdx.x, (unsigned long long)t);
-    }
-}
-
-// One wavefront per row.  out row = corrected row; n_cand[r] = number of correctable positions.  GLOBAL = false: the
-// list lives in LDS, a row with more than MSA_MAX_CAND positions gets n_cand = -1 and is left for the second launch;
-// GLOBAL = true: rows come from `row_list` (n_list of them) and keep their lists in g_freq / g_col (ncols entries per row).
-template <bool GLOBAL>
-__global__ __launch_bounds__(256) void k_msa_row_correct(const uint8_t *__restrict__ M, uint8_t *__restrict__ out, uint32_t nr, uint32_t ncols,
-                                                          const int32_t *__restrict__ degree, const int32_t *__restrict__ counts,
-                                                          const uint8_t *__restrict__ maj, const uint8_t *__restrict__ flags,
-                                                          const unsigned long long *__restrict__ class_tot, int32_t *__restrict__ n_cand,
-                                                          const uint32_t *__restrict__ row_list, uint32_t n_list, double *g_freq, uint32_t *g_col)
-{
-    __shared__ double s_freq[GLOBAL ? 1 : 4][GLOBAL ? 1 : MSA_MAX_CAND];
-    __shared__ uint32_t s_col[GLOBAL ? 1 : 4][GLOBAL ? 1 : MSA_MAX_CAND];
+    constexpr bool GLOBAL = CAP == MSA_LIST_HBM;
+    __shared__ double s_freq[GLOBAL ? 1 : 4][GLOBAL ? 1 : CAP];
+    __shared__ uint32_t s_col[GLOBAL ? 1 : 4][GLOBAL ? 1 : CAP];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t slot = blockIdx.x * 4 + wave;
-    if (slot >= (GLOBAL ? n_list : nr)) return;
+    if (slot >= (GLOBAL ? n_list : B.n_rows)) return;
     const uint32_t r = GLOBAL ? row_list[slot] : slot;
-    const uint32_t cap = GLOBAL ? ncols : (uint32_t)MSA_MAX_CAND;
-    const uint8_t *row = M + (size_t)r * ncols;
-    uint8_t *orow = out + (size_t)r * ncols;
+    const uint32_t p = B.part_of_row[r], ncols = B.ncols[p];
+    const uint32_t cap = GLOBAL ? ncols : (uint32_t)CAP;
+    const size_t cell0 = B.m_off[p] + (size_t)(r - B.first_row[p]) * ncols;
+    const uint8_t *row = M_all + cell0;
+    uint8_t *orow = out_all + cell0;
+    const int32_t *counts = counts_all + (size_t)5 * B.col_base[p];
+    const uint8_t *maj = maj_all + B.col_base[p], *flags = flags_all + B.col_base[p];
+    const unsigned long long *class_tot = class_tot_all + (size_t)3 * p;
     const char SYM[5] = {'A', 'C', 'G', 'T', '-'};
     const double d_ins = (double)(class_tot[0] > 0 ? class_tot[0] : 1ull);
     const double d_del = (double)(class_tot[1] > 0 ? class_tot[1] : 1ull);
     const double d_sub = (double)(class_tot[2] > 0 ? class_tot[2] : 1ull);
     const bool single = degree[r] == 1;
-    double *fq = GLOBAL ? g_freq + (size_t)slot * ncols : s_freq[wave];
-    uint32_t *cl = GLOBAL ? g_col + (size_t)slot * ncols : s_col[wave];
+    double *fq = GLOBAL ? g_freq + (size_t)slot * list_stride : s_freq[wave];
+    uint32_t *cl = GLOBAL ? g_col + (size_t)slot * list_stride : s_col[wave];
     uint32_t n = 0;                 // candidates so far (wave-uniform)
     bool overflow = false;
     for (uint32_t c0 = 0; c0 < ncols; c0 += 64) {
@@ -125,12 +342,10 @@ __global__ __launch_bounds__(256) void k_msa_row_correct(const uint8_t *__restri
         const unsigned long long mask = __ballot(cand);
         if (mask) {
             const uint32_t at = n + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-            if (cand) {
-                if (at < cap) {
-                    const int mj = maj[col];
-                    const double own = (double)counts[(size_t)msa_sym(v) * ncols + col];
-                    msa_put<GLOBAL>(fq, cl, at, own / (mj == 4 ? d_ins : (v == '-' ? d_del : d_sub)), col);
-                }
+            if (cand && at < cap) {
+                const int mj = maj[col];
+                const double own = (double)counts[(size_t)msa_sym(v) * ncols + col];
+                msa_put<GLOBAL>(fq, cl, at, own / (mj == 4 ? d_ins : (v == '-' ? d_del : d_sub)), col);
             }
             n += (uint32_t)__popcll(mask);
             if (n > cap) overflow = true;
@@ -167,25 +382,26 @@ __global__ __launch_bounds__(256) void k_msa_row_correct(const uint8_t *__restri
         if (msa_freq<GLOBAL>(fq, i) <= thr) { const uint32_t c = msa_col<GLOBAL>(cl, i); orow[c] = (uint8_t)SYM[maj[c]]; }
 }
 
-__global__ __launch_bounds__(256) void k_msa_row_lengths(const uint8_t *__restrict__ rows, uint32_t nr, uint32_t ncols, uint32_t *__restrict__ len)
+__global__ __launch_bounds__(256) void k_msa_row_lengths(const uint8_t *__restrict__ rows_all, MsaBatch B, uint32_t *__restrict__ len)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t r = blockIdx.x * 4 + wave;
-    if (r >= nr) return;
-    const uint8_t *row = rows + (size_t)r * ncols;
+    if (r >= B.n_rows) return;
+    const uint32_t p = B.part_of_row[r], ncols = B.ncols[p];
+    const uint8_t *row = rows_all + B.m_off[p] + (size_t)(r - B.first_row[p]) * ncols;
     uint32_t c = 0;
     for (uint32_t col = lane; col < ncols; col += 64) c += row[col] != '-';
     for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
     if (lane == 0) len[r] = c;
 }
 
-__global__ __launch_bounds__(256) void k_msa_strip(const uint8_t *__restrict__ rows, uint32_t nr, uint32_t ncols, const uint64_t *__restrict__ off,
-                                                    uint8_t *__restrict__ packed)
+__global__ __launch_bounds__(256) void k_msa_strip(const uint8_t *__restrict__ rows_all, MsaBatch B, const uint64_t *__restrict__ off, uint8_t *__restrict__ packed)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t r = blockIdx.x * 4 + wave;
-    if (r >= nr) return;
-    const uint8_t *row = rows + (size_t)r * ncols;
+    if (r >= B.n_rows) return;
+    const uint32_t p = B.part_of_row[r], ncols = B.ncols[p];
+    const uint8_t *row = rows_all + B.m_off[p] + (size_t)(r - B.first_row[p]) * ncols;
     uint8_t *dst = packed + off[r];
     uint32_t at = 0;
     for (uint32_t c0 = 0; c0 < ncols; c0 += 64) {

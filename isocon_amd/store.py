@@ -257,7 +257,7 @@ class SeqStore(object):
             _lib.check(rc, "isocon_nn_finalize_dev")
             return out_best[:n], row_ptr.astype(np.int64), cols[:int(row_ptr[n])]
 
-    # ---- consensus correction with the multi-alignment matrix built on the device (csrc/msa_build.hpp) ----------
+    # ---- consensus correction with the multi-alignment matrix built on the device (csrc/msa.hpp) ----------------
     def msa_build_ops(self, row_ids, ops, ops_ptr):
         """The partition row_ids[0] (centre) + row_ids[1:] (members) with the members' CIGAR ops against the centre (ops_ptr[0] = ops_ptr[1] = 0)
         -> (n_cols, col_slot uint32[Lm + 1], longest uint32[Lm + 1], wide uint32[k, 8] = row, slot, position in the member, length, 2-bit codes

@@ -223,6 +223,9 @@ def correct_cases():
         ("noisy_5x256", *noisy(5, 256, 16)),
         ("noisy_9x257", *noisy(9, 257, 17, heavy=[(0, 2)])),
         ("noisy_300x1000", *noisy(300, 1000, 18, heavy=[(0, 7)])),
+        # more than one 256-row chunk of the column counts AND more than one 256-column block; rows of degree 2, 3, 50 on both sides of the chunk boundary
+        ("noisy_257x513_heavy_rows", *noisy(257, 513, 19, heavy=[(0, 2), (255, 3), (256, 50)])),
+        ("noisy_513x257_heavy_rows", *noisy(513, 257, 20, heavy=[(255, 2), (256, 3), (511, 50)])),
         ("a_two_way_ties_2x1", *two_way_ties(1, 21)),
         ("a_two_way_ties_2x65", *two_way_ties(65, 22)),
         ("b_subset_ties_5x65", *subset_ties(5, 65, 23)[:2]),

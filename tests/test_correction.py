@@ -105,7 +105,7 @@ def test_device_correction_equals_host_statement(monkeypatch):
 @pytest.mark.gpu
 @pytest.mark.parametrize("profile", ["ccs", "ont"])
 def test_device_built_matrix_equals_the_host_matrix(profile):
-    """isocon_msa_build_ops (the multi-alignment matrix from CIGAR ops and the packed store, csrc/msa_build.hpp) + the wide-slot patches
+    """isocon_msa_build_ops (the multi-alignment matrix from CIGAR ops and the packed store, csrc/msa.hpp) + the wide-slot patches
     against functions.msa_matrix on the gapped strings (the reference's layout, functions.py:543-588,679-767): every cell of every
     partition; CCS-like reads (single-base insertions) and reads with many multi-base insertions (wide slots)."""
     import numpy as np

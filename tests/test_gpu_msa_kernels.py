@@ -1,4 +1,4 @@
-"""The consensus-correction kernels (csrc/msa.hpp, msa_build.hpp, msa_batch.hpp) and their entry points (msa_host.inc) against the numpy
+"""The consensus-correction kernels (csrc/msa.hpp) and their entry points (msa_host.inc) against the numpy
 checker (oracle/correction.py) and the host matrix (functions.msa_matrix), on the designed inputs of tests/msa_cases.py: column ties,
 gap majorities, zero class totals, frequency ties, the limits of the LDS candidate lists (2048; 1024 in the batched kernel, with the
 single-partition repeat of correction_module), centres at the 1024-slot step of the layout scan, rows with more than 64 ops, insertions

@@ -107,6 +107,26 @@ def test_heavy_rows(nr, ncols, seed):
         assert (plain != maj).sum() > 5
 
 
+@pytest.mark.parametrize("name", ["noisy_257x513_heavy_rows", "noisy_513x257_heavy_rows"])
+def test_row_chunks_and_column_blocks_together(name):
+    """a second 256-row chunk of the column counts and a second 256-column block in one matrix, both with a tail; rows of degree 2, 3 and 50 on
+    both sides of the chunk boundary; the last chunk's rows change the class totals, the last block's columns hold candidates"""
+    M, deg = {c[0]: c[1:] for c in MC.correct_cases()}[name]
+    nr, ncols = M.shape
+    assert sorted((nr, ncols)) == [257, 513]
+    heavy = np.flatnonzero(deg != 1)
+    assert sorted(deg[heavy].tolist()) == [2, 3, 50] and heavy.min() < 256 <= heavy.max() and deg[heavy.max()] == 50
+    r_last, c_last = 256 * (nr // 256), 256 * (ncols // 256)
+    assert 0 < nr - r_last < 256 and 0 < ncols - c_last < 256
+    maj, unamb = OC.column_majority(M, deg)
+    packed, off, n_cand = OC.correct_rows(M, deg)
+    assert (n_cand[heavy] == 0).all() and (n_cand[deg == 1] > 0).all()
+    cand = (M != maj) & unamb
+    assert cand[deg == 1][:, c_last:].any() and cand[heavy].any()          # (the heavy rows carry errors that are counted, never corrected)
+    assert OC.class_totals(M[:r_last], deg[:r_last]) != OC.class_totals(M, deg)
+    assert (M[r_last:] != maj)[:, unamb].any()          # (the last chunk's rows put counts into minority symbols)
+
+
 @pytest.mark.parametrize("name", sorted(MC.TIE_SPECS))
 def test_frequency_ties(name):
     spec = MC.TIE_SPECS[name]
