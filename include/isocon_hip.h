@@ -372,6 +372,25 @@ int isocon_hw_pairs_wide(isocon_store *s, const uint32_t *q, const uint32_t *t, 
                          int32_t *out, float *kernel_ms);
 
 /*
+ * edlib.align(q, t, mode="NW", task="path", k) for a pair list (modules/edlib_alignment_module.py:130-135 edlib_traceback).
+ * k NULL or k[p] < 0: unbounded.  out_ed[p] = distance, or -1 above k (then the pair has no ops).  Pair p owns
+ * out_ops[out_ops_ptr[p] .. out_ops_ptr[p + 1]), len << 4 | code (0 '=', 1 'X', 2 'I' query only, 3 'D' target only), forward order,
+ * adjacent ops differ, none empty.  Which optimal path is reported is the oracle's tie rule (from the end cell: 'I', then 'D', then the
+ * diagonal; oracle/isocon_oracle.c orc_nw_path).  ISOCON_E_CAPACITY + *needed when ops_cap is too small (out_ed and out_ops_ptr are
+ * valid then).
+ * The distances come first, through the implementation of isocon_ed_pairs; only the pairs within their threshold are traced, by
+ * un-banded kernels (one wavefront per pair, the whole query in 64-row blocks against the whole target, 16 bytes of trace per block
+ * and column: about len_q * len_t / 4 bytes).  The traces of one launch stay within 1 GiB of scratch: the list is cut into as many
+ * launches as that takes, and a single pair that needs more on its own is refused with ISOCON_E_UNSUPPORTED (isocon_last_error states
+ * its sizes).  So is a query of more than 4 096 bases against a target of more than 655 360.  A pair with an empty sequence is answered
+ * on the host (one 'D' or one 'I' op; none when both are empty).  A store under its own map of at most four symbols works unchanged
+ * (only equality matters); one with more than four symbols returns ISOCON_E_ALPHABET; ids out of range ISOCON_E_ARG.
+ * *kernel_ms sums the distance and the path kernels.
+ */
+int isocon_ed_path_pairs(isocon_store *s, const uint32_t *q, const uint32_t *t, const int32_t *k, uint64_t n_pairs,
+                         int32_t *out_ed, uint32_t *out_ops, uint64_t *out_ops_ptr, uint64_t ops_cap, uint64_t *needed, float *kernel_ms);
+
+/*
  * Device read tables of the hypothesis test: which reads support a candidate against its reference, and every read's error counts,
  * from the stored read alignments -- the per-read loops of get_support (modules/functions.py:149-201), get_read_errors (:204-216) and
  * read_errors_from_alignment (:495-522) as arrange_alignments_new_no_realign calls them per edge (modules/hypothesis_test_module.py:92-171).

@@ -106,29 +106,58 @@ def edlib_alignment_helper(arguments):
     return edlib_alignment(*args, **kwargs)
 
 
+# which route edlib_traceback took, per call: the device (isocon_ed_path_pairs) or the host (functions.nw_path_cigar)
+TRACEBACK_STATS = {"device": 0, "host": 0}
+
+
+def _cigar_of_steps(steps):
+    cigar, i = [], 0
+    while i < len(steps):
+        j = i
+        while j < len(steps) and steps[j] == steps[i]:
+            j += 1
+        cigar.append("%d%s" % (j - i, steps[i]))
+        i = j
+    return "".join(cigar)
+
+
 def edlib_traceback(x, y, mode="NW", task="path", k=1):
     """EAM:130-135: (editDistance, locations, cigar) of edlib.align(x, y, mode="NW", task="path", k=k).  Its only caller
-    (isocon_statistical_test.get_nearest_neighbor_graph, :63-104) is never called in v0.3.3.  The
-    k-bounded distance comes from the GPU; above k edlib reports (-1, [], None).  The path of a hit is traced on the host
-    (functions.nw_path_cigar, O(len x * len y): this is not a hot path) with the tie rule used everywhere else (from the
-    end: I, then D, then the diagonal; "parity unpinned").  HW mode lives in end_invariant_functions.edlib_traceback."""
+    (isocon_statistical_test.get_nearest_neighbor_graph, :63-104) is never called in v0.3.3.  Distance
+    and path come from the GPU (SeqStore.ed_path_pairs: the k-bounded distance first, the path of a hit from the un-banded
+    trace kernels), with the tie rule used everywhere else (from the end: I, then D, then the diagonal; "parity unpinned");
+    above k edlib reports (-1, [], None).  Two cases stay on the host (functions.nw_path_cigar, a full matrix in Python:
+    short sequences only): a pair that holds more than four distinct symbols (the path kernels run on the 2-bit planes;
+    its distance still comes from the GPU), and a machine without a GPU.  TRACEBACK_STATS counts the calls per route.
+    HW mode lives in end_invariant_functions.edlib_traceback."""
     if mode != "NW" or task != "path":
         raise NotImplementedError("edlib_alignment_module.edlib_traceback: only mode='NW', task='path' (EAM:130-135)")
-    from .store import SeqStore
-    st = SeqStore([x, y])
-    try:
-        ed = int(st.ed_pairs([0], [1], None if k is None or k < 0 else [int(k)])[0])
-    finally:
-        st.close()
-    if ed < 0:
-        return -1, [], None
+    kk = None if k is None or k < 0 else int(k)
+    have_gpu = _lib.load().isocon_device_count() > 0
+    if have_gpu and len(set(x) | set(y)) <= 4:
+        st = SeqStore([x, y])
+        try:
+            ed, ops, _ = st.ed_path_pairs([0], [1], None if kk is None else [kk])
+        finally:
+            st.close()
+        TRACEBACK_STATS["device"] += 1
+        if ed[0] < 0:
+            return -1, [], None
+        return int(ed[0]), [(0, len(y) - 1)], "".join("%d%s" % (o >> 4, "=XID"[o & 15]) for o in ops.tolist())
     from .functions import nw_path_cigar
-    ops = nw_path_cigar(x, y)
-    cigar, i = [], 0
-    while i < len(ops):
-        j = i
-        while j < len(ops) and ops[j] == ops[i]:
-            j += 1
-        cigar.append("%d%s" % (j - i, ops[i]))
-        i = j
-    return ed, [(0, len(y) - 1)], "".join(cigar)
+    TRACEBACK_STATS["host"] += 1
+    if have_gpu:
+        st = SeqStore([x, y])
+        try:
+            ed = int(st.ed_pairs([0], [1], None if kk is None else [kk])[0])
+        finally:
+            st.close()
+        if ed < 0:
+            return -1, [], None
+        steps = nw_path_cigar(x, y)
+    else:
+        steps = nw_path_cigar(x, y)
+        ed = sum(1 for c in steps if c != "=")
+        if kk is not None and ed > kk:
+            return -1, [], None
+    return ed, [(0, len(y) - 1)], _cigar_of_steps(steps)

@@ -194,6 +194,23 @@ def edlib_traceback(x, y, mode="HW", task="path", k=1, end_threshold=0):
     return int(_ends_adjusted(res, [len(y)], end_threshold)[0])
 
 
+def edlib_traceback_allow_ends(x, y, mode="NW", task="path", k=1, end_threshold=0):
+    """end_invariant_functions.py:191-223: the global alignment of edlib_alignment_module.edlib_traceback with the distance reduced by
+    the leading and by the trailing I / D run when that run is no longer than the threshold (each end on its own, as there: a path
+    that is ONE such run counts at both ends).  Returns (ed, locations, cigar); above k (-1, [], None)."""
+    if mode != "NW" or task != "path":
+        raise NotImplementedError("end_invariant_functions.edlib_traceback_allow_ends: only mode='NW', task='path'")
+    from .edlib_alignment_module import edlib_traceback as nw_traceback
+    ed, locations, cigar = nw_traceback(x, y, mode=mode, task=task, k=k)
+    if cigar:
+        import re
+        runs = re.findall(r"(\d+)([=XID])", cigar)
+        for length, op in (runs[0], runs[-1]):
+            if op in "ID" and int(length) <= end_threshold:
+                ed -= int(length)
+    return ed, locations, cigar
+
+
 def _window_pairs(lens, q_lo, q_hi, window, depth):
     """Neighbour indices the loop of get_all_NN visits for every query q_lo <= i < q_hi, in its order (offset j = 1, 2, ...:
     i - j, then i + j; either side stops for good at the first length difference above `window` or at the list's end,

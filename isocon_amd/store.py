@@ -108,6 +108,32 @@ class SeqStore(object):
                                            _ptr(out, _lib.i32p), ctypes.byref(ms)), "isocon_ed_pairs")
         return (out, ms.value) if return_ms else out
 
+    def ed_path_pairs(self, q, t, k=None, return_ms=False):
+        """edlib.align(q[p], t[p], mode="NW", task="path", k[p]) for a pair list (isocon_ed_path_pairs): (ed int32[n] -- -1 above k --,
+        ops uint32[], ops_ptr uint64[n + 1]); pair p owns ops[ops_ptr[p]:ops_ptr[p + 1]], len << 4 | code (0 '=', 1 'X', 2 'I' query
+        only, 3 'D' target only) in forward order.  k: None (unbounded), a scalar or one value per pair (negative: unbounded)."""
+        q = np.ascontiguousarray(q, dtype=np.uint32)
+        t = np.ascontiguousarray(t, dtype=np.uint32)
+        if len(q) != len(t):
+            raise ValueError("pair arrays differ in length")
+        n = len(q)
+        kk = None if k is None else np.ascontiguousarray(np.broadcast_to(np.asarray(k, dtype=np.int32), q.shape))
+        ed = np.full(n, -1, dtype=np.int32)
+        ops_ptr = np.zeros(n + 1, dtype=np.uint64)
+        cap = min(256 * n, 1 << 26) + 1024     # generous (untouched pages of np.empty cost nothing): a too-small buffer means tracing again
+        needed = ctypes.c_uint64(0)
+        ms = ctypes.c_float(0)
+        while True:
+            ops = np.empty(cap, dtype=np.uint32)
+            rc = self._L.isocon_ed_path_pairs(self._h, _ptr(q, _lib.u32p), _ptr(t, _lib.u32p), _ptr(kk, _lib.i32p), n, _ptr(ed, _lib.i32p),
+                                              _ptr(ops, _lib.u32p), _ptr(ops_ptr, _lib.u64p), cap, ctypes.byref(needed), ctypes.byref(ms))
+            if rc == _lib.ISOCON_E_CAPACITY:
+                cap = int(needed.value) + 16
+                continue
+            _lib.check(rc, "isocon_ed_path_pairs")
+            out = (ed, ops[:int(ops_ptr[n])], ops_ptr)
+            return out + (ms.value,) if return_ms else out
+
     def qgram_bound_pairs(self, a, b):
         """Lower bounds of ed(a[i], b[i]) from q-gram count profiles (csrc/qgram_mm.hpp) -- the pre-filter of the NN main pass."""
         a = np.ascontiguousarray(a, dtype=np.uint32)
