@@ -391,6 +391,25 @@ int isocon_ed_path_pairs(isocon_store *s, const uint32_t *q, const uint32_t *t, 
                          int32_t *out_ed, uint32_t *out_ops, uint64_t *out_ops_ptr, uint64_t ops_cap, uint64_t *needed, float *kernel_ms);
 
 /*
+ * edlib.align(q, t, mode="HW", task="path", k) for a pair list: where inside the target the query sits and how it aligns there.
+ * out (n_pairs, 5) holds exactly the rows of isocon_hw_pairs_wide for the same arguments (distance or -1, start, end, leading /
+ * trailing insertion run), with that entry's checks and statuses: k[p] >= 0 required, k[p] > 2^20 ISOCON_E_UNSUPPORTED, ids out of
+ * range ISOCON_E_ARG, a store of more than four symbols ISOCON_E_ALPHABET, an empty sequence a row of -1.  A pair with out[5 p] >= 0
+ * owns out_ops[out_ops_ptr[p] .. out_ops_ptr[p + 1]), ops as in isocon_ed_path_pairs (len << 4 | code, 0 '=', 1 'X', 2 'I' query only,
+ * 3 'D' target only; forward order, adjacent ops differ, none empty): the global alignment of the query against t[start..end] under the
+ * oracle's tie rule (from the end cell: 'I', then 'D', then the diagonal; oracle.hw_path).  A pair above its threshold has no ops.
+ * ISOCON_E_CAPACITY + *needed when ops_cap is too small (out and out_ops_ptr are valid then).
+ * Two stages: the rows come through the implementation of isocon_hw_pairs_wide (banded kernels where the band fits), then every hit is
+ * traced over its window alone by the un-banded kernel of isocon_ed_path_pairs (16 bytes of trace per 64-row block and window column;
+ * the target outside the window is not stored).  The traces of one launch stay within 1 GiB of scratch: the hits are cut into as many
+ * launches as that takes, and a pair that needs more on its own is refused with ISOCON_E_UNSUPPORTED (isocon_last_error states its
+ * sizes).  So is a query of more than 4 096 bases against a window of more than 655 360.  *kernel_ms sums both stages.
+ */
+int isocon_hw_path_pairs(isocon_store *s, const uint32_t *q, const uint32_t *t, const int32_t *k, uint64_t n_pairs,
+                         int32_t *out /* n_pairs x 5 */, uint32_t *out_ops, uint64_t *out_ops_ptr, uint64_t ops_cap,
+                         uint64_t *needed, float *kernel_ms);
+
+/*
  * Device read tables of the hypothesis test: which reads support a candidate against its reference, and every read's error counts,
  * from the stored read alignments -- the per-read loops of get_support (modules/functions.py:149-201), get_read_errors (:204-216) and
  * read_errors_from_alignment (:495-522) as arrange_alignments_new_no_realign calls them per edge (modules/hypothesis_test_module.py:92-171).

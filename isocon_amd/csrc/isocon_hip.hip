@@ -134,7 +134,7 @@ enum {
     SLOT_PACK_ASCII, SLOT_PACK_OFF, SLOT_PACK_BAD, SLOT_PACK_HIST, SLOT_PACK_FLAGS, SLOT_EB_A, SLOT_EB_B, SLOT_EB_K, SLOT_EB_OUT, SLOT_EB_ROWS, SLOT_SCAN_TMP, SLOT_SCAN_SUMS,
     SLOT_RT_REF, SLOT_RT_IN, SLOT_RT_OUT,
     SLOT_EV_IN, SLOT_EV_OUT, SLOT_EV_SNIP,
-    SLOT_NWP_Q, SLOT_NWP_T, SLOT_NWP_ED, SLOT_NWP_TOFF, SLOT_NWP_ROFF, SLOT_NWP_REV, SLOT_NWP_RUNS, SLOT_NWP_FOFF, SLOT_NWP_OPS,
+    SLOT_NWP_Q, SLOT_NWP_T, SLOT_NWP_ED, SLOT_NWP_TOFF, SLOT_NWP_ROFF, SLOT_NWP_REV, SLOT_NWP_RUNS, SLOT_NWP_FOFF, SLOT_NWP_OPS, SLOT_NWP_START, SLOT_NWP_COLS,
     SLOT_COUNT
 };
 static_assert(SLOT_COUNT <= 160, "ScratchPool::slots too small");
@@ -1022,6 +1022,7 @@ extern "C" int isocon_block_bound_pairs(isocon_store *s, const uint32_t *owner, 
 #include "hw_host.inc"
 #include "hw_full_host.inc"
 #include "nw_path_host.inc"
+#include "hw_path_host.inc"
 #include "readtab_host.inc"
 #include "edgevar_host.inc"
 

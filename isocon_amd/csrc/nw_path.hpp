@@ -2,9 +2,12 @@
 // (the reference's modules/edlib_alignment_module.py:130-135, edlib_traceback).  Lane-level math, the walk and the op encoding:
 // nw_path_core.hpp; the forward pass and the layout of the trace store: hw_full.hpp / hw_full_core.hpp.
 //
-// The distances are known when these kernels run (isocon_ed_pairs' path, bounded by k): only the pairs within their threshold get here.
-//   k_nwp_trace  one wavefront = one pair.  hwf_run<HWF_TRACE> over the WHOLE target with every column kept (start = 0, ms = len t,
-//                top-row delta +1), un-banded; its score must equal the known distance.  Then the wave-uniform walk from (m, n): one
+// The distances are known when these kernels run (isocon_ed_pairs' path, bounded by k; for the infix entry isocon_hw_pairs_wide's,
+// with the location): only the pairs within their threshold get here.
+//   k_nwp_trace<WINDOW>  one wavefront = one pair.  hwf_run<HWF_TRACE> with every column kept and the top-row delta +1, un-banded,
+//                over the WHOLE target (WINDOW = false: start = 0, ms = len t; isocon_ed_path_pairs) or over the located window
+//                t[t_start .. t_start + t_cols) alone (WINDOW = true: isocon_hw_path_pairs, the global alignment of the query
+//                against that window); its score must equal the known distance.  Then the wave-uniform walk from (m, ms): one
 //                request brings 64 columns of the current block -- lane c holds Pv / Ph and the text base of column j - c -- and the
 //                block's two query plane words, so telling '=' from 'X' costs no further trip.  Lane 0 writes the runs, REVERSED, into
 //                the pair's slice of 2 ed + 1 ops (nwp_max_runs) and the number of runs.
@@ -20,13 +23,16 @@ namespace isocon {
 struct NwpIn {
     const uint32_t *pq, *pt;     // query / target of the launch's pairs
     const int32_t *ed;           // their distances
+    const int32_t *t_start;      // WINDOW only: first target position of every pair's window, and its number of columns; the store
+    const int32_t *t_cols;       //              is that of (m, t_cols)
     const uint64_t *trace_off;   // first 16-byte unit of every pair's trace store within the launch's scratch
     const uint64_t *rev_off;     // first op of every pair's slice of the reversed runs
     uint32_t n;
 };
 
 // out_runs[x] = number of runs of pair x, or an internal status: -5 the pass' score is not the known distance, -6 more runs than
-// 2 ed + 1.  grid = in.n blocks of 64 threads.
+// 2 ed + 1, -7 (WINDOW) the window is not inside the target.  grid = in.n blocks of 64 threads.
+template <bool WINDOW>
 __global__ __launch_bounds__(64) void k_nwp_trace(DevStore S, NwpIn in, ulonglong2 *__restrict__ trace_all, uint32_t *__restrict__ rev_all,
                                                    int32_t *__restrict__ out_runs)
 {
@@ -38,15 +44,18 @@ __global__ __launch_bounds__(64) void k_nwp_trace(DevStore S, NwpIn in, ulonglon
     if (blockIdx.x >= in.n) return;
     const uint32_t x = blockIdx.x;
     const uint32_t q = (uint32_t)uniform_i32((int32_t)in.pq[x]), tid = (uint32_t)uniform_i32((int32_t)in.pt[x]);
-    const int32_t m = uniform_i32(S.lens[q]), n = uniform_i32(S.lens[tid]), ed = uniform_i32(in.ed[x]);
+    const int32_t m = uniform_i32(S.lens[q]), nt = uniform_i32(S.lens[tid]), ed = uniform_i32(in.ed[x]);
+    // the columns of the pass are target positions ts .. ts + n - 1
+    const int32_t ts = WINDOW ? uniform_i32(in.t_start[x]) : 0, n = WINDOW ? uniform_i32(in.t_cols[x]) : nt;
     int32_t r = -5;
-    if (m > 0 && n > 0 && ed >= 0) {
+    if (WINDOW && (ts < 0 || n <= 0 || n > nt - ts)) r = -7;
+    else if (m > 0 && n > 0 && ed >= 0) {
         ulonglong2 *trace = trace_all + in.trace_off[x];
         uint32_t *rev = rev_all + in.rev_off[x];
         const int32_t cap = (int32_t)nwp_max_runs(ed);
         auto text = [&](int32_t s, uint32_t &wl, uint32_t &wh) {
-            wl = hw_text32(pw, S.n, S.nchunks, tid, 0, s);
-            wh = hw_text32(pw, S.n, S.nchunks, tid, 1, s);
+            wl = hw_text32(pw, S.n, S.nchunks, tid, 0, ts + s);
+            wh = hw_text32(pw, S.n, S.nchunks, tid, 1, ts + s);
         };
         int32_t sc, best, col;
         hwf_run<HWF_TRACE>(S, q, m, n, ed, text, nwp_bound, trace, true, sc, best, col);
@@ -61,7 +70,7 @@ __global__ __launch_bounds__(64) void k_nwp_trace(DevStore S, NwpIn in, ulonglon
                     qlo = planes[((size_t)b * nseq + q) * 2]; qhi = planes[((size_t)b * nseq + q) * 2 + 1];
                     if (jj >= 1) {
                         const ulonglong2 u = trace[hwf_trace_unit(m, n, b, jj)];
-                        const int32_t p = jj - 1;
+                        const int32_t p = ts + jj - 1;
                         const uint64_t tl = planes[((size_t)(p >> 6) * nseq + tid) * 2], th = planes[((size_t)(p >> 6) * nseq + tid) * 2 + 1];
                         cpv = u.x; cph = u.y;
                         cbase = (int32_t)((tl >> (p & 63)) & 1) | ((int32_t)((th >> (p & 63)) & 1) << 1);

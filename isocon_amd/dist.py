@@ -490,3 +490,49 @@ def sharded_sg_trace(store, a, b, mismatch, match=2, open_=2, ext=0, tie_policy=
             out_ops[out_ptr[p]:out_ptr[p + 1]] = o[src_ptr[i]:src_ptr[i + 1]]
             out_res[p] = rr[i]
     return out_ops, out_ptr, out_res
+
+
+def sharded_path_pairs(store, q, t, k=None, infix=False, dist=None, device=None):
+    """Alignment paths of the pairs computed by all ranks (each a round-robin share), gathered everywhere: infix=False the global
+    paths of SeqStore.ed_path_pairs -- (ed, ops, ops_ptr) --, infix=True the infix paths of SeqStore.hw_path_pairs -- (rows, ops,
+    ops_ptr) --, in the caller's pair order.  k: None (unbounded), a scalar or one value per pair.  The ops travel as one ragged int32
+    all_gather, like those of sharded_sg_trace."""
+    import torch
+    if dist is None:
+        import torch.distributed as dist  # noqa: PLC0415
+    world, rank = dist.get_world_size(), dist.get_rank()
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
+    q = np.asarray(q, dtype=np.uint32); t = np.asarray(t, dtype=np.uint32)
+    n = len(q)
+    kk = np.ascontiguousarray(np.broadcast_to(np.asarray(-1 if k is None else k, dtype=np.int32), q.shape))
+    lens = np.asarray(store.lens)
+    if not same_everywhere(_digest(q, t, kk, np.asarray([getattr(store, "fingerprint", 0), int(bool(infix))], dtype=np.int64)), dist, device):
+        raise RuntimeError("sharded_path_pairs: the ranks hold different pair lists / sequence sets")
+    shards = _pair_shards(lens[q], lens[t], world)
+    mine = shards[rank]
+    width = 5 if infix else 1
+    if len(mine):
+        head, ops, ptr = (store.hw_path_pairs if infix else store.ed_path_pairs)(q[mine], t[mine], kk[mine])
+    else:
+        head, ops, ptr = np.zeros((0, width), np.int32), np.zeros(0, np.uint32), np.zeros(1, np.uint64)
+    cnt = np.diff(np.asarray(ptr).astype(np.int64)).astype(np.int32)
+    g_ops = _all_gather_ragged(dist, np.ascontiguousarray(ops, dtype=np.uint32).view(np.int32), device)
+    g_cnt = _all_gather_ragged(dist, cnt, device)
+    g_head = _all_gather_ragged(dist, np.ascontiguousarray(head, dtype=np.int32).reshape(-1), device)
+    counts = np.zeros(n, dtype=np.int64)
+    for r in range(world):
+        counts[shards[r]] = g_cnt[r]
+    out_ptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(counts, out=out_ptr[1:])
+    out_ops = np.empty(int(out_ptr[n]), dtype=np.uint32)
+    out_head = np.empty((n, width), dtype=np.int32)
+    for r in range(world):
+        src_ptr = np.zeros(len(shards[r]) + 1, dtype=np.int64)
+        np.cumsum(g_cnt[r], out=src_ptr[1:])
+        hh = g_head[r].reshape(-1, width)
+        o = g_ops[r].view(np.uint32)
+        for i, p in enumerate(shards[r].tolist()):
+            out_ops[out_ptr[p]:out_ptr[p + 1]] = o[src_ptr[i]:src_ptr[i + 1]]
+            out_head[p] = hh[i]
+    return (out_head if infix else out_head.reshape(-1)), out_ops, out_ptr.astype(np.uint64)

@@ -108,6 +108,9 @@ def edlib_alignment_helper(arguments):
 
 # which route edlib_traceback took, per call: the device (isocon_ed_path_pairs) or the host (functions.nw_path_cigar)
 TRACEBACK_STATS = {"device": 0, "host": 0}
+# the calls of edlib_traceback_infix (isocon_hw_path_pairs; it has the device route alone).  A dict of its own: TRACEBACK_STATS holds
+# exactly the two routes of edlib_traceback, and its callers compare it whole
+TRACEBACK_INFIX_STATS = {"device": 0}
 
 
 def _cigar_of_steps(steps):
@@ -161,3 +164,22 @@ def edlib_traceback(x, y, mode="NW", task="path", k=1):
         if kk is not None and ed > kk:
             return -1, [], None
     return ed, [(0, len(y) - 1)], _cigar_of_steps(steps)
+
+
+def edlib_traceback_infix(x, y, k=1):
+    """(editDistance, locations, cigar) of edlib.align(x, y, mode="HW", task="path", k=k): where x sits inside y and how it aligns
+    there -- what the reference's barcode-style callers of edlib_traceback(mode="HW", task="path") read.  locations holds the one
+    (start, end) the other infix entry points report; the cigar is the global alignment of x against y[start:end + 1] under the tie rule
+    used everywhere else (from the end: I, then D, then the diagonal).  k None or negative: unbounded.  Above k: (-1, [], None), as is
+    an empty x or y.  Everything comes from the GPU (SeqStore.hw_path_pairs) and there is no host route: a machine without a GPU, or a
+    pair with more than four distinct symbols, raises IsoconError, as the infix entry points do.  A name of its own, because
+    edlib_traceback(mode="HW") keeps raising NotImplementedError."""
+    st = SeqStore([x, y])
+    try:
+        rows, ops, _ = st.hw_path_pairs([0], [1], None if k is None or k < 0 else [int(k)])
+    finally:
+        st.close()
+    TRACEBACK_INFIX_STATS["device"] += 1
+    if rows[0, 0] < 0:
+        return -1, [], None
+    return int(rows[0, 0]), [(int(rows[0, 1]), int(rows[0, 2]))], "".join("%d%s" % (o >> 4, "=XID"[o & 15]) for o in ops.tolist())

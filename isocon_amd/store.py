@@ -134,6 +134,37 @@ class SeqStore(object):
             out = (ed, ops[:int(ops_ptr[n])], ops_ptr)
             return out + (ms.value,) if return_ms else out
 
+    def hw_path_pairs(self, q, t, k=None, return_ms=False):
+        """edlib.align(q[p], t[p], mode="HW", task="path", k[p]) for a pair list (isocon_hw_path_pairs): (rows int32[n, 5] -- those of
+        hw_pairs(wide=True): distance or -1, start, end, leading / trailing insertion run --, ops uint32[], ops_ptr uint64[n + 1]); a hit
+        p owns ops[ops_ptr[p]:ops_ptr[p + 1]], the global alignment of q[p] against t[p][start:end + 1], encoded as in ed_path_pairs.
+        k: a scalar or one value per pair; None or a negative value: unbounded (sent as len(q[p]), which an infix distance never
+        exceeds)."""
+        q = np.ascontiguousarray(q, dtype=np.uint32)
+        t = np.ascontiguousarray(t, dtype=np.uint32)
+        if len(q) != len(t):
+            raise ValueError("pair arrays differ in length")
+        n = len(q)
+        # (an id out of range is the library's to refuse)
+        qlen = np.take(np.asarray(self.lens, dtype=np.int64), q, mode="clip") if self.n else np.zeros(n, dtype=np.int64)
+        kk = np.broadcast_to(np.asarray(-1 if k is None else k, dtype=np.int64), q.shape)
+        kk = np.ascontiguousarray(np.where(kk < 0, qlen, kk).clip(max=2 ** 31 - 1), dtype=np.int32)
+        rows = np.full((n, 5), -1, dtype=np.int32)
+        ops_ptr = np.zeros(n + 1, dtype=np.uint64)
+        cap = min(256 * n, 1 << 26) + 1024     # (as ed_path_pairs)
+        needed = ctypes.c_uint64(0)
+        ms = ctypes.c_float(0)
+        while True:
+            ops = np.empty(cap, dtype=np.uint32)
+            rc = self._L.isocon_hw_path_pairs(self._h, _ptr(q, _lib.u32p), _ptr(t, _lib.u32p), _ptr(kk, _lib.i32p), n, _ptr(rows, _lib.i32p),
+                                              _ptr(ops, _lib.u32p), _ptr(ops_ptr, _lib.u64p), cap, ctypes.byref(needed), ctypes.byref(ms))
+            if rc == _lib.ISOCON_E_CAPACITY:
+                cap = int(needed.value) + 16
+                continue
+            _lib.check(rc, "isocon_hw_path_pairs")
+            out = (rows, ops[:int(ops_ptr[n])], ops_ptr)
+            return out + (ms.value,) if return_ms else out
+
     def qgram_bound_pairs(self, a, b):
         """Lower bounds of ed(a[i], b[i]) from q-gram count profiles (csrc/qgram_mm.hpp) -- the pre-filter of the NN main pass."""
         a = np.ascontiguousarray(a, dtype=np.uint32)
