@@ -83,6 +83,10 @@ uint32_t isocon_store_size(const isocon_store *s);
  * ranks of a sharded run compare it before they split the work (isocon_amd/dist.py). */
 int isocon_store_digest(const isocon_store *s, uint64_t *out);
 uint64_t isocon_store_device_bytes(const isocon_store *s);
+/* Blocking host waits -- synchronous copies and memsets, event and device synchronisations -- of the last nearest-neighbour call on
+ * this store (isocon_nn_graph, isocon_nn_partial, isocon_nn_partial_dev): what is left of them is what the search needs an answer
+ * from the device for ("How the step is fed to the device"). */
+uint64_t isocon_nn_last_host_waits(const isocon_store *s);
 
 /*
  * Batched global (NW) edit distance over an explicit pair list.

@@ -8,6 +8,7 @@
 #include <numeric>
 #include <string>
 #include <memory>
+#include <mutex>
 #include <thread>
 #include <vector>
 
@@ -126,7 +127,7 @@ struct ScratchPool {
 
 enum {
     SLOT_ED_TS = 0, SLOT_ED_IDS, SLOT_ED_K, SLOT_ED_OUT, SLOT_FULL_A, SLOT_FULL_B, SLOT_FULL_K, SLOT_FULL_OUT,
-    SLOT_NN_BEST, SLOT_NN_QF, SLOT_NN_TF, SLOT_NN_HITS, SLOT_NN_HITCOUNT, SLOT_NN_STATS, SLOT_NN_TS, SLOT_NN_IDS, SLOT_NN_PLANES2, SLOT_NN_PERM, SLOT_NN_IL, SLOT_NN_IL2, SLOT_NN_HITS2, SLOT_NN_HITCOUNT2, SLOT_NN_QPROF, SLOT_NN_QSUM, SLOT_NN_LB, SLOT_NN_LBROW, SLOT_NN_LBLEN, SLOT_NN_SLOTORDER, SLOT_NN_LBCHUNKS, SLOT_NN_ROWMIN, SLOT_NN_COLMIN, SLOT_NN_SEED_A, SLOT_NN_SEED_B, SLOT_NN_SEED_N, SLOT_NN_LBT, SLOT_NN_LBT_OFF, SLOT_NN_LBT_SLO, SLOT_NN_LBT_LEN, SLOT_NN_LBT_PAD, SLOT_NN_SCORE, SLOT_NN_LDEST, SLOT_NN_FIN_HITS, SLOT_NN_FIN_CNT, SLOT_NN_FIN_START, SLOT_NN_FIN_CUR, SLOT_NN_FIN_NB, SLOT_NN_FIN_LEN2, SLOT_NN_FIN_ROWPTR, SLOT_NN_FIN_COLS, SLOT_NN_FIN_FLAG, SLOT_NN_FIN_BEST, SLOT_NN_ACC_HITS, SLOT_NN_LTOT, SLOT_NN_LCHUNKS, SLOT_NN_LIST, SLOT_NN_LPA, SLOT_NN_LPB, SLOT_NN_TEXT2, SLOT_NN_LTASKS,
+    SLOT_NN_BEST, SLOT_NN_QF, SLOT_NN_TF, SLOT_NN_HITS, SLOT_NN_HITCOUNT, SLOT_NN_STATS, SLOT_NN_TS, SLOT_NN_IDS, SLOT_NN_PLANES2, SLOT_NN_PERM, SLOT_NN_IL, SLOT_NN_IL2, SLOT_NN_HITS2, SLOT_NN_HITCOUNT2, SLOT_NN_QPROF, SLOT_NN_QSUM, SLOT_NN_LB, SLOT_NN_LBROW, SLOT_NN_LBLEN, SLOT_NN_SLOTORDER, SLOT_NN_LBCHUNKS, SLOT_NN_ROWMIN, SLOT_NN_COLMIN, SLOT_NN_SEED_A, SLOT_NN_SEED_B, SLOT_NN_SEED_N, SLOT_NN_LBT, SLOT_NN_LBT_OFF, SLOT_NN_LBT_SLO, SLOT_NN_LBT_LEN, SLOT_NN_LBT_PAD, SLOT_NN_SCORE, SLOT_NN_LDEST, SLOT_NN_FIN_HITS, SLOT_NN_FIN_CNT, SLOT_NN_FIN_START, SLOT_NN_FIN_CUR, SLOT_NN_FIN_NB, SLOT_NN_FIN_LEN2, SLOT_NN_FIN_OUT, SLOT_NN_FIN_FLAG, SLOT_NN_FIN_BEST, SLOT_NN_ACC_HITS, SLOT_NN_LTOT, SLOT_NN_LCHUNKS, SLOT_NN_LIST, SLOT_NN_LPA, SLOT_NN_LPB, SLOT_NN_TEXT2, SLOT_NN_LTASKS, SLOT_NN_RECORD,
     SLOT_NN2_STATE, SLOT_NN2_TPOS, SLOT_NN2_EXC, SLOT_NN2_CTR, SLOT_NN2_PAIRS, SLOT_NN2_WIDE,
     SLOT_SG_PAIRS, SLOT_SG_R, SLOT_SG_TRACE, SLOT_SG_END, SLOT_SG_OPS, SLOT_SG_CNT, SLOT_SG_RES, SLOT_SG_OFF, SLOT_SG_DENSE, SLOT_SG_BOUND, SLOT_SG_AOFF, SLOT_SG_ALNA, SLOT_SG_ALNB,
     SLOT_MSA_IN, SLOT_MSA_OUT, SLOT_MSA_DEG, SLOT_MSA_COUNTS, SLOT_MSA_MAJ, SLOT_MSA_FLAGS, SLOT_MSA_TOT, SLOT_MSA_NCAND, SLOT_MSA_LEN, SLOT_MSA_OFF, SLOT_MSA_PACKED, SLOT_MSA_ROWS, SLOT_MSA_OPS, SLOT_MSA_OPTR, SLOT_MSA_LONGEST, SLOT_MSA_WIDTH, SLOT_MSA_CSLOT, SLOT_MSA_LTOT, SLOT_MSA_WIDE, SLOT_MSA_PROW, SLOT_MSA_PCOL, SLOT_MSA_PPTR, SLOT_MSA_PBYTES, SLOT_MSA_PART, SLOT_MSA_FIRST, SLOT_MSA_LM, SLOT_MSA_SBASE, SLOT_MSA_NCOLS, SLOT_MSA_MOFF, SLOT_MSA_CBASE, SLOT_MSA_CBP, SLOT_MSA_CBC, SLOT_MSA_CBR,
@@ -175,6 +176,7 @@ struct isocon_store {
     bool is_exc(uint32_t i) const { return n_exc != 0 && exc[i] != 0; }
     int32_t *d_lens = nullptr;
     int32_t maxlen = 0;
+    uint64_t last_host_waits = 0;          // isocon_nn_last_host_waits
 };
 
 namespace {
@@ -212,14 +214,21 @@ static bool is_pinned(const void *p, size_t bytes)
     return false;
 }
 
+// Blocking host waits of the entry point that is running -- every synchronous copy or memset, every event or device synchronise that
+// the nearest-neighbour paths issue goes through one of the helpers below (isocon_nn_last_host_waits reports the last call's count).
+static thread_local uint64_t g_host_waits = 0;
+static hipError_t memcpy_wait(void *dst, const void *src, size_t bytes, hipMemcpyKind kind) { ++g_host_waits; return hipMemcpy(dst, src, bytes, kind); }
+static hipError_t memset_wait(void *dst, int value, size_t bytes) { ++g_host_waits; return hipMemset(dst, value, bytes); }
+static hipError_t device_wait() { ++g_host_waits; return hipDeviceSynchronize(); }
+
 static hipError_t copy_d2h(void *dst, const void *dsrc, size_t bytes)
 {
-    if (bytes < kStageMin || is_pinned(dst, bytes)) return hipMemcpy(dst, dsrc, bytes, hipMemcpyDeviceToHost);
+    if (bytes < kStageMin || is_pinned(dst, bytes)) return memcpy_wait(dst, dsrc, bytes, hipMemcpyDeviceToHost);
     char *st = static_cast<char *>(g_stage.get(kStageBytes));
-    if (!st) return hipMemcpy(dst, dsrc, bytes, hipMemcpyDeviceToHost);
+    if (!st) return memcpy_wait(dst, dsrc, bytes, hipMemcpyDeviceToHost);
     for (size_t off = 0; off < bytes; off += kStageBytes) {
         const size_t len = std::min(kStageBytes, bytes - off);
-        const hipError_t e = hipMemcpy(st, static_cast<const char *>(dsrc) + off, len, hipMemcpyDeviceToHost);
+        const hipError_t e = memcpy_wait(st, static_cast<const char *>(dsrc) + off, len, hipMemcpyDeviceToHost);
         if (e != hipSuccess) return e;
         memcpy(static_cast<char *>(dst) + off, st, len);
     }
@@ -228,17 +237,55 @@ static hipError_t copy_d2h(void *dst, const void *dsrc, size_t bytes)
 
 static hipError_t copy_h2d(void *ddst, const void *src, size_t bytes)
 {
-    if (bytes < kStageMin || is_pinned(src, bytes)) return hipMemcpy(ddst, src, bytes, hipMemcpyHostToDevice);
+    if (bytes < kStageMin || is_pinned(src, bytes)) return memcpy_wait(ddst, src, bytes, hipMemcpyHostToDevice);
     char *st = static_cast<char *>(g_stage.get(kStageBytes));
-    if (!st) return hipMemcpy(ddst, src, bytes, hipMemcpyHostToDevice);
+    if (!st) return memcpy_wait(ddst, src, bytes, hipMemcpyHostToDevice);
     for (size_t off = 0; off < bytes; off += kStageBytes) {
         const size_t len = std::min(kStageBytes, bytes - off);
         memcpy(st, static_cast<const char *>(src) + off, len);
-        const hipError_t e = hipMemcpy(static_cast<char *>(ddst) + off, st, len, hipMemcpyHostToDevice);
+        const hipError_t e = memcpy_wait(static_cast<char *>(ddst) + off, st, len, hipMemcpyHostToDevice);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
+
+// The one side stream of the library: the row layout of the bound matrix (NNContext::build_bounds) goes up on it from pinned memory of
+// its own while the profile kernel runs on the null stream, which then waits for `done` instead of the host waiting for three copies.
+// Like g_stage it is the process' only one and takes no lock: one process drives one device and runs one search at a time.
+struct SideUpload {
+    hipStream_t stream = nullptr;
+    hipEvent_t before = nullptr, done = nullptr;
+    PinnedStage pinned;
+    bool in_flight = false;
+    bool ready()
+    {
+        if (stream) return true;
+        if (hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) { stream = nullptr; (void)hipGetLastError(); return false; }
+        if (hipEventCreateWithFlags(&before, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess) {
+            (void)hipGetLastError();
+            release();
+            return false;
+        }
+        return true;
+    }
+    // the pinned block may be written again once the copies that read it are through
+    void settle()
+    {
+        if (!in_flight) return;
+        // (a call that failed between its first copy and the record of `done` leaves an event that says nothing: the stream itself is asked)
+        if (hipEventQuery(done) != hipSuccess || hipStreamQuery(stream) != hipSuccess) { (void)hipGetLastError(); ++g_host_waits; (void)hipStreamSynchronize(stream); }
+        in_flight = false;
+    }
+    void release()
+    {
+        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+        if (before) (void)hipEventDestroy(before);
+        if (done) (void)hipEventDestroy(done);
+        stream = nullptr; before = done = nullptr; in_flight = false;
+        pinned.release();
+    }
+};
+static SideUpload g_side;
 
 struct DevBuf {
     void *p = nullptr;
@@ -277,24 +324,102 @@ static int device_exscan(ScratchPool *pl, const uint32_t *d_in, uint32_t n, OUT 
     return ISOCON_OK;
 }
 
+// Events of the phase timers: created once, handed out and taken back (a call records ~30 of them; hipEventCreate per interval would
+// cost more than the waits the deferred timing removes).
+struct EventPool {
+    std::mutex mu;
+    std::vector<hipEvent_t> idle;
+    hipEvent_t get()
+    {
+        {
+            std::lock_guard<std::mutex> g(mu);
+            if (!idle.empty()) { hipEvent_t e = idle.back(); idle.pop_back(); return e; }
+        }
+        hipEvent_t e = nullptr;
+        if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        return e;
+    }
+    void put(hipEvent_t e)
+    {
+        if (!e) return;
+        std::lock_guard<std::mutex> g(mu);
+        idle.push_back(e);
+    }
+    void release()
+    {
+        std::lock_guard<std::mutex> g(mu);
+        for (hipEvent_t e : idle) (void)hipEventDestroy(e);
+        idle.clear();
+    }
+};
+static EventPool g_events;
+
+// HIP-event time of the launches between start() and a stop.  start(), mark() and stop_later() only record events on the null stream:
+// every interval owns its events, and resolve() -- once per entry point, behind a wait the call needs anyway -- turns the intervals
+// into milliseconds: each is added to `total`, to the field its stop_later() named, and the part behind its mark() to the second
+// field (to `marked_total` when none was named).  stop() is the blocking form: it resolves at once and returns its interval.
+// ISOCON_DEBUG_VARIANT=nn_sync_phases: every stop_later() waits, as every phase did before the intervals were deferred (A/B runs, tests).
 struct EventTimer {
-    hipEvent_t e0 = nullptr, e1 = nullptr, em = nullptr;
+    struct Interval { hipEvent_t e0, em, e1; float *acc, *marked_acc; };
+    std::vector<Interval> pending;
+    hipEvent_t e0 = nullptr, em = nullptr;          // of the open interval
     float total = 0.f;
-    float marked_total = 0.f;      // time between a mark() and the stop() that follows it, summed (a second launch inside one start / stop pair,
-    bool marked = false;           // timed without a host synchronisation between the two launches)
-    bool ok = false;
-    EventTimer() { ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess && hipEventCreate(&em) == hipSuccess; }
-    ~EventTimer() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); if (em) (void)hipEventDestroy(em); }
-    void start() { if (ok) (void)hipEventRecord(e0, 0); marked = false; }
-    void mark() { if (ok) { (void)hipEventRecord(em, 0); marked = true; } }
+    float marked_total = 0.f;
+    const bool sync_phases = variant("nn_sync_phases");
+    EventTimer() {}
+    EventTimer(const EventTimer &) = delete;
+    EventTimer &operator=(const EventTimer &) = delete;
+    ~EventTimer()
+    {
+        g_events.put(e0); g_events.put(em);
+        for (const Interval &iv : pending) { g_events.put(iv.e0); g_events.put(iv.em); g_events.put(iv.e1); }
+    }
+    void start()
+    {
+        g_events.put(em); em = nullptr;
+        if (!e0) e0 = g_events.get();
+        if (e0) (void)hipEventRecord(e0, 0);
+    }
+    void mark()
+    {
+        if (!e0) return;
+        if (!em) em = g_events.get();
+        if (em) (void)hipEventRecord(em, 0);
+    }
+    void stop_later(float *acc, float *marked_acc = nullptr)
+    {
+        if (!e0) return;
+        hipEvent_t e1 = g_events.get();
+        if (!e1) { g_events.put(e0); g_events.put(em); e0 = em = nullptr; return; }
+        (void)hipEventRecord(e1, 0);
+        pending.push_back(Interval{e0, em, e1, acc, marked_acc});
+        e0 = em = nullptr;
+        if (sync_phases) resolve(true);
+    }
+    // the pointers handed to stop_later() must still be good here
+    void resolve(bool wait_counts = false)
+    {
+        if (pending.empty()) return;
+        hipEvent_t last = pending.back().e1;          // (one stream: the last recorded event completes last)
+        if (wait_counts || hipEventQuery(last) != hipSuccess) { (void)hipGetLastError(); ++g_host_waits; (void)hipEventSynchronize(last); }
+        for (const Interval &iv : pending) {
+            float ms = 0.f, part = 0.f;
+            if (hipEventElapsedTime(&ms, iv.e0, iv.e1) != hipSuccess) { (void)hipGetLastError(); ms = 0.f; }
+            total += ms;
+            if (iv.acc) *iv.acc += ms;
+            if (iv.em) {
+                if (hipEventElapsedTime(&part, iv.em, iv.e1) != hipSuccess) { (void)hipGetLastError(); part = 0.f; }
+                if (iv.marked_acc) *iv.marked_acc += part; else marked_total += part;
+            }
+            g_events.put(iv.e0); g_events.put(iv.em); g_events.put(iv.e1);
+        }
+        pending.clear();
+    }
     float stop()
     {
         float ms = 0.f;
-        if (ok) {
-            (void)hipEventRecord(e1, 0); (void)hipEventSynchronize(e1); (void)hipEventElapsedTime(&ms, e0, e1);
-            if (marked) { float part = 0.f; (void)hipEventElapsedTime(&part, em, e1); marked_total += part; marked = false; }
-        }
-        total += ms;
+        stop_later(&ms);
+        resolve(true);
         return ms;
     }
 };
@@ -368,7 +493,7 @@ int isocon_device_count(void)
     return n;
 }
 
-void isocon_release_scratch(void) { g_scratch.release(); g_stage.release(); }
+void isocon_release_scratch(void) { g_scratch.release(); g_stage.release(); g_events.release(); g_side.release(); }
 
 int isocon_init(int device_ordinal)
 {
@@ -628,6 +753,7 @@ void isocon_store_destroy(isocon_store *s)
 }
 
 uint32_t isocon_store_size(const isocon_store *s) { return s ? s->dev.n : 0; }
+uint64_t isocon_nn_last_host_waits(const isocon_store *s) { return s ? s->last_host_waits : 0; }
 uint64_t isocon_store_device_bytes(const isocon_store *s) { return s ? s->device_bytes : 0; }
 
 }  // extern "C"

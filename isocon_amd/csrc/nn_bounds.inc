@@ -28,15 +28,17 @@ int NNContext::build_bounds(const QMap &Q, int32_t kcap, NNParams &P, bool want_
     d_qprof.slot = SLOT_NN_QPROF; d_qsum.slot = SLOT_NN_QSUM;
     HostClock bclk;
     {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || prof_bytes > free_b / 2 + st->pool.slots[SLOT_NN_QPROF].cap) return ISOCON_OK;
+        size_t free_b = 0;
+        if (!free_mem(free_b) || prof_bytes > free_b / 2 + st->pool.slots[SLOT_NN_QPROF].cap) return ISOCON_OK;
         if (d_qprof.alloc(prof_bytes) || d_qsum.alloc((size_t)n * 4)) return ISOCON_OK;
     }
     bclk.lap("bounds: memory check + profile buffers");
+    // (the side stream's uploads below start behind everything the null stream holds at this point, not behind the profile kernel)
+    const bool side = !variant("nn_sync_uploads") && g_side.ready() && hipEventRecord(g_side.before, 0) == hipSuccess;
     tm.start();
     hipLaunchKernelGGL(k_qgram_profile4, dim3((n + QP_SEQS - 1) / QP_SEQS), dim3(256), 0, 0, st->dev, d_qprof.as<uint8_t>(), d_qsum.as<uint32_t>(), n_pad);
     ISO_HIP_CHECK(hipGetLastError());
-    struct StopTimer { NNContext &c; bool armed = true; ~StopTimer() { if (armed) c.stats.bound_kernel_ms += c.tm.stop(); } } stop_timer{*this};
+    struct StopTimer { NNContext &c; bool armed = true; ~StopTimer() { if (armed) c.tm.stop_later(&c.stats.bound_kernel_ms); } } stop_timer{*this};
     // Row s of the matrix = launch slot s of the main pass = entry q = Q.entry(s), its columns the neighbours
     // p = q + 1 .. q + rlen[s]; the kernels address column p as lb[off[s] + (p - q - 1)].  A row's storage starts at a 16-byte
     // boundary with column (q + 1) & ~15 and ends with column ((q + rlen) | 15), so the address of column p is congruent to
@@ -74,9 +76,9 @@ int NNContext::build_bounds(const QMap &Q, int32_t kcap, NNParams &P, bool want_
     // bound of its size: the cells are those of the matrix, a row pads at most 30 bytes.
     const unsigned long long totalT = sum_rlen + 30ull * n;
     bclk.lap("bounds: transposed rows (host)");
-    size_t free_b = 0, total_b = 0;
+    size_t free_b = 0;
     const size_t need = (size_t)total + (size_t)totalT + prof_bytes + (size_t)n * 24 + (size_t)nq * 12;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || need > free_b / 2 + st->pool.slots[SLOT_NN_LB].cap + st->pool.slots[SLOT_NN_QPROF].cap) return ISOCON_OK;
+    if (!free_mem(free_b) || need > free_b / 2 + st->pool.slots[SLOT_NN_LB].cap + st->pool.slots[SLOT_NN_QPROF].cap) return ISOCON_OK;
     // Tile table of k_qgram_mm: 256 x 256 tiles in super-tiles of 4 row blocks x 8 column blocks = 32 entries (0xffffffff = no
     // tile); the kernel hands the 32 entries of a super-tile to workgroups that share an XCD, so a super-tile loads 12 operand
     // panels from beyond L2 instead of 64.
@@ -116,9 +118,27 @@ int NNContext::build_bounds(const QMap &Q, int32_t kcap, NNParams &P, bool want_
     d_chunks.pool = &st->pool;
     d_chunks.slot = SLOT_NN_LBCHUNKS;
     if (d_chunks.alloc(tiles.size() * sizeof(uint2))) return ISOCON_OK;
-    ISO_HIP_CHECK(copy_h2d(d_chunks.p, tiles.data(), tiles.size() * sizeof(uint2)));
-    ISO_HIP_CHECK(copy_h2d(d_lbrow.p, off.data(), (size_t)nq * 8));
-    ISO_HIP_CHECK(copy_h2d(d_lblen.p, rlen.data(), (size_t)nq * 4));
+    // tile table, row offsets and row lengths: staged in pinned memory and copied on the side stream while the profile kernel runs; the
+    // null stream waits for them in front of k_lbt_rows, the host does not wait at all
+    const size_t b_tiles = (tiles.size() * sizeof(uint2) + 15) & ~(size_t)15, b_off = ((size_t)nq * 8 + 15) & ~(size_t)15, b_len = (size_t)nq * 4;
+    char *pin = nullptr;
+    if (side) { g_side.settle(); pin = static_cast<char *>(g_side.pinned.get(b_tiles + b_off + b_len)); }
+    if (pin) {
+        memcpy(pin, tiles.data(), tiles.size() * sizeof(uint2));
+        memcpy(pin + b_tiles, off.data(), (size_t)nq * 8);
+        memcpy(pin + b_tiles + b_off, rlen.data(), (size_t)nq * 4);
+        g_side.in_flight = true;          // (from the first copy on: an error below must not let the next call write the block unsettled)
+        ISO_HIP_CHECK(hipStreamWaitEvent(g_side.stream, g_side.before, 0));
+        ISO_HIP_CHECK(hipMemcpyAsync(d_chunks.p, pin, tiles.size() * sizeof(uint2), hipMemcpyHostToDevice, g_side.stream));
+        ISO_HIP_CHECK(hipMemcpyAsync(d_lbrow.p, pin + b_tiles, (size_t)nq * 8, hipMemcpyHostToDevice, g_side.stream));
+        ISO_HIP_CHECK(hipMemcpyAsync(d_lblen.p, pin + b_tiles + b_off, (size_t)nq * 4, hipMemcpyHostToDevice, g_side.stream));
+        ISO_HIP_CHECK(hipEventRecord(g_side.done, g_side.stream));
+        ISO_HIP_CHECK(hipStreamWaitEvent(0, g_side.done, 0));
+    } else {
+        ISO_HIP_CHECK(copy_h2d(d_chunks.p, tiles.data(), tiles.size() * sizeof(uint2)));
+        ISO_HIP_CHECK(copy_h2d(d_lbrow.p, off.data(), (size_t)nq * 8));
+        ISO_HIP_CHECK(copy_h2d(d_lblen.p, rlen.data(), (size_t)nq * 4));
+    }
     hipLaunchKernelGGL(k_lbt_rows, dim3((n + 255) / 256), dim3(256), 0, 0, Q, nq, d_lblen.as<uint32_t>(), n, d_sloT.as<uint32_t>(), d_lenT.as<uint32_t>(), d_padT.as<uint32_t>());
     if ((rc = device_exscan<0, unsigned long long>(&st->pool, d_padT.as<uint32_t>(), n, d_offT.as<unsigned long long>()))) return ISOCON_OK;
     hipLaunchKernelGGL(k_lbt_offsets, dim3((n + 255) / 256), dim3(256), 0, 0, n, d_sloT.as<uint32_t>(), d_offT.as<unsigned long long>());
@@ -159,13 +179,8 @@ int NNContext::build_bounds(const QMap &Q, int32_t kcap, NNParams &P, bool want_
                        d_lbt.as<uint8_t>(), d_score.as<uint32_t>());
     ISO_HIP_CHECK(hipGetLastError());
     stop_timer.armed = false;
-    {
-        const float before = tm.marked_total;
-        stats.bound_kernel_ms += tm.stop();
-        stats.mm_kernel_ms += tm.marked_total - before;
-        tm.marked_total = before;          // (the context's marked time is the narrow table launch's: narrow_kernel_ms)
-    }
-    bclk.lap("bounds: k_qgram_mm (wait)");
+    tm.stop_later(&stats.bound_kernel_ms, &stats.mm_kernel_ms);          // (the context's own marked time is the narrow table launch's: narrow_kernel_ms)
+    bclk.lap("bounds: k_qgram_mm (enqueued)");
 #ifdef ISOCON_QM_TIMELINE
     {
         const size_t nt = std::min<size_t>(tiles.size(), 16384);
@@ -225,7 +240,7 @@ int NNContext::run_bound_seeds(const QMap &Q)
     hipLaunchKernelGGL(k_ed_lanes<true>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, 0, st->dev, params(63), d_seed_a.as<uint32_t>(), d_seed_b.as<uint32_t>(),
                        (const int32_t *)nullptr, np, (int32_t *)nullptr);
     ISO_HIP_CHECK(hipGetLastError());
-    stats.seed_kernel_ms += tm.stop();
+    tm.stop_later(&stats.seed_kernel_ms);
     return ISOCON_OK;
 }
 

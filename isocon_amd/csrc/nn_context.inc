@@ -45,21 +45,46 @@ struct NNContext {
     isocon_nn_stats stats;
     EventTimer tm;
 
-    // nibble rows padded to the longest sequence; false if that is not affordable (callers fall back to other kernels)
-    bool ensure_text()
+    // free device memory, asked for once per entry point (the pool only grows: what a later phase finds can only be less by what an
+    // earlier one took, and every check below leaves half of it alone)
+    size_t free_bytes = 0;
+    int free_state = 0;          // 0: not asked yet, 1: known, -1: the query failed
+    bool free_mem(size_t &free_b)
     {
-        if (text_ready) return true;
+        if (free_state == 0) {
+            size_t total_b = 0;
+            free_state = hipMemGetInfo(&free_bytes, &total_b) == hipSuccess ? 1 : -1;
+            if (free_state < 0) (void)hipGetLastError();
+        }
+        free_b = free_bytes;
+        return free_state > 0;
+    }
+    // nibble rows padded to the longest sequence, in two steps: text_affordable() -- false if there is no room for them (callers fall
+    // back to other kernels) -- and build_text(), immediately before the first launch that reads them (a call whose survivors all go
+    // to the pair-per-lane kernel never writes them).
+    bool text_room = false;
+    bool text_affordable()
+    {
+        if (text_ready || text_room) return true;
         text_stride = (uint32_t)NN_TEXT_PAD_FRONT + (uint32_t)((st->maxlen + 7) / 8) + (uint32_t)NN_TEXT_PAD_BACK;
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || (size_t)n * text_stride * 4 > free_b / 2) return false;
+        size_t free_b = 0;
+        if (!free_mem(free_b) || (size_t)n * text_stride * 4 > free_b / 2) return false;
         d_text.pool = &st->pool;
         d_text.slot = SLOT_NN_IL;
         if (d_text.alloc((size_t)std::max<uint32_t>(n, 1) * text_stride * 4) != ISOCON_OK) return false;
+        text_room = true;
+        return true;
+    }
+    bool build_text()
+    {
+        if (text_ready) return true;
+        if (!text_room) return false;
         hipLaunchKernelGGL(k_build_nibble_text, dim3(std::max<uint32_t>(n, 1)), dim3(256), 0, 0, st->dev, d_text.as<uint32_t>(), text_stride);
-        if (hipGetLastError() != hipSuccess) return false;
+        if (hipGetLastError() != hipSuccess) { g_last_error = "k_build_nibble_text: launch failed"; return false; }
         text_ready = true;
         return true;
     }
+    bool ensure_text() { return text_affordable() && build_text(); }
     // 2-bit texts of the block filter (nn_filter.hpp), built on first use
     DevBuf d_text2;
     uint32_t text2_stride = 0;
@@ -68,8 +93,8 @@ struct NNContext {
     {
         if (text2_ready) return true;
         text2_stride = nnf_text2_stride(st->maxlen);
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || (size_t)n * text2_stride * 4 > free_b / 2 + st->pool.slots[SLOT_NN_TEXT2].cap) return false;
+        size_t free_b = 0;
+        if (!free_mem(free_b) || (size_t)n * text2_stride * 4 > free_b / 2 + st->pool.slots[SLOT_NN_TEXT2].cap) return false;
         d_text2.pool = &st->pool;
         d_text2.slot = SLOT_NN_TEXT2;
         if (d_text2.alloc((size_t)std::max<uint32_t>(n, 1) * text2_stride * 4) != ISOCON_OK) return false;
@@ -133,14 +158,42 @@ struct NNContext {
         return P;
     }
 
-    int upload_best() { ISO_HIP_CHECK(copy_h2d(d_best.p, best.data(), (size_t)n * 4)); return ISOCON_OK; }
-    int download_best() { ISO_HIP_CHECK(copy_d2h(best.data(), d_best.p, (size_t)n * 4)); return ISOCON_OK; }
+    // fill_best: the caller gave no bounds and the host mirror still holds NN_INF everywhere -- the next upload is a fill on the device
+    // (isocon_nn_graph sets it in front of the 64-row phase; one upload consumes it)
+    bool fill_best = false;
+    bool best_on_host = true;          // false: a phase left its bounds on the device only (isocon_nn_graph fetches them with the CSR)
+    int upload_best()
+    {
+        if (fill_best) {
+            fill_best = false;
+            if (n) ISO_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)d_best.p, NN_INF, n, 0));
+            return ISOCON_OK;
+        }
+        ISO_HIP_CHECK(copy_h2d(d_best.p, best.data(), (size_t)n * 4));
+        return ISOCON_OK;
+    }
+    int download_best() { ISO_HIP_CHECK(copy_d2h(best.data(), d_best.p, (size_t)n * 4)); best_on_host = true; return ISOCON_OK; }
     // d_stats: two counter blocks -- [0] every launch but the 32-row table launch, [1] that one (nn_phase_a)
+    static constexpr uint32_t N_COUNTERS = 2 * (NN_COUNTER_SLOTS * 4 + 1);
     int reset_counters()
     {
-        ISO_HIP_CHECK(hipMemset(d_hit_count.p, 0, 8));
-        ISO_HIP_CHECK(hipMemset(d_stats.p, 0, 2 * (NN_COUNTER_SLOTS * 4 + 1) * 8));
+        ISO_HIP_CHECK(hipMemsetAsync(d_hit_count.p, 0, 8, 0));
+        ISO_HIP_CHECK(hipMemsetAsync(d_stats.p, 0, N_COUNTERS * 8, 0));
         return ISOCON_OK;
+    }
+    void add_counters(const unsigned long long *sc2)
+    {
+        for (int blk = 0; blk < 2; ++blk) {
+            const unsigned long long *sc = sc2 + blk * (NN_COUNTER_SLOTS * 4 + 1);
+            stats.pairs_prefiltered += sc[NN_COUNTER_SLOTS * 4];
+            for (int i = 0; i < NN_COUNTER_SLOTS; ++i) {
+                stats.pairs_evaluated += sc[i * 4 + 0];
+                stats.cells_columns += sc[i * 4 + 1];
+                stats.tiles += sc[i * 4 + 2];
+                stats.live_columns += sc[i * 4 + 3];
+                if (blk == 1) stats.narrow_columns += sc[i * 4 + 1];
+            }
+        }
     }
     // pulls device hits into `out`; returns ISOCON_E_CAPACITY if the device list overflowed.  filter: drop on the device
     // every hit whose distance is above the endpoint's current best[] (it can never be part of the answer).
@@ -151,20 +204,10 @@ struct NNContext {
     int collect(std::vector<int32_t> &out, uint64_t *needed, bool filter = false, bool to_device = false)
     {
         unsigned long long cnt = 0;
-        ISO_HIP_CHECK(hipMemcpy(&cnt, d_hit_count.p, 8, hipMemcpyDeviceToHost));
-        unsigned long long sc2[2][NN_COUNTER_SLOTS * 4 + 1];
-        ISO_HIP_CHECK(hipMemcpy(sc2, d_stats.p, sizeof(sc2), hipMemcpyDeviceToHost));
-        for (int blk = 0; blk < 2; ++blk) {
-            const unsigned long long *sc = sc2[blk];
-            stats.pairs_prefiltered += sc[NN_COUNTER_SLOTS * 4];
-            for (int i = 0; i < NN_COUNTER_SLOTS; ++i) {
-                stats.pairs_evaluated += sc[i * 4 + 0];
-                stats.cells_columns += sc[i * 4 + 1];
-                stats.tiles += sc[i * 4 + 2];
-                stats.live_columns += sc[i * 4 + 3];
-                if (blk == 1) stats.narrow_columns += sc[i * 4 + 1];
-            }
-        }
+        ISO_HIP_CHECK(memcpy_wait(&cnt, d_hit_count.p, 8, hipMemcpyDeviceToHost));
+        unsigned long long sc2[N_COUNTERS];
+        ISO_HIP_CHECK(memcpy_wait(sc2, d_stats.p, sizeof(sc2), hipMemcpyDeviceToHost));
+        add_counters(sc2);
         if (needed) *needed = cnt;
         if (cnt > hits_cap) return ISOCON_E_CAPACITY;
         stats.hits += cnt;
@@ -173,12 +216,12 @@ struct NNContext {
             DevBuf d_h2(&st->pool, SLOT_NN_HITS2), d_c2(&st->pool, SLOT_NN_HITCOUNT2);
             int rc;
             if ((rc = d_h2.alloc((size_t)cnt * 12)) || (rc = d_c2.alloc(8))) return rc;
-            ISO_HIP_CHECK(hipMemset(d_c2.p, 0, 8));
+            ISO_HIP_CHECK(hipMemsetAsync(d_c2.p, 0, 8, 0));
             const unsigned blocks = (unsigned)std::min<unsigned long long>((cnt + 255) / 256, 4096);
             hipLaunchKernelGGL(k_filter_hits, dim3(blocks), dim3(256), 0, 0, d_hits.as<int32_t>(), cnt, d_best.as<int32_t>(), d_h2.as<int32_t>(),
                                d_c2.as<unsigned long long>());
             ISO_HIP_CHECK(hipGetLastError());
-            ISO_HIP_CHECK(hipMemcpy(&cnt, d_c2.p, 8, hipMemcpyDeviceToHost));
+            ISO_HIP_CHECK(memcpy_wait(&cnt, d_c2.p, 8, hipMemcpyDeviceToHost));
             src = d_h2.p;
         }
         if (to_device) {
@@ -189,6 +232,34 @@ struct NNContext {
         const size_t base = out.size();
         out.resize(base + (size_t)cnt * 3);
         if (cnt) ISO_HIP_CHECK(copy_d2h(out.data() + base, src, (size_t)cnt * 12));
+        return ISOCON_OK;
+    }
+    // The end of the 64-row phase when the CSR kernels follow on the device (csr_follows, set by isocon_nn_graph): the hit count, the
+    // counters and "does the wide-band phase have to run" come back as ONE record; hits and bounds stay where they are.  The list is
+    // not filtered: the CSR kernels keep exactly the hits that attain their endpoint's bound (nn_fin_valid), stale ones included or not.
+    // The price is paid by the rare fallbacks -- phase B has to run, or a row is too long for the device sort: pull_dev_hits then brings
+    // the unfiltered list to the host (several times the bytes k_filter_hits used to leave; nn_finalize_impl drops the stale hits itself).
+    bool csr_follows = false;
+    bool wide_needed = false;
+    int collect_record(uint64_t *needed)
+    {
+        DevBuf d_rec(&st->pool, SLOT_NN_RECORD);
+        int rc;
+        if ((rc = d_rec.alloc((2 + N_COUNTERS) * 8))) return rc;
+        ISO_HIP_CHECK(hipMemsetAsync(d_rec.p, 0, 16, 0));
+        hipLaunchKernelGGL(k_nn_step_record, dim3(std::max<uint32_t>(1, (n + 255) / 256)), dim3(256), 0, 0, d_hit_count.as<unsigned long long>(), d_stats.as<unsigned long long>(),
+                           N_COUNTERS, d_best.as<int32_t>(), d_qf.as<uint8_t>(), st->dev.lens, n, d_rec.as<unsigned long long>());
+        ISO_HIP_CHECK(hipGetLastError());
+        unsigned long long rec[2 + N_COUNTERS];
+        ISO_HIP_CHECK(memcpy_wait(rec, d_rec.p, sizeof(rec), hipMemcpyDeviceToHost));
+        add_counters(rec + 2);
+        if (needed) *needed = rec[0];
+        if (rec[0] > hits_cap) return ISOCON_E_CAPACITY;
+        stats.hits += rec[0];
+        wide_needed = rec[1] != 0;
+        dev_hits = d_hits.as<int32_t>();
+        dev_hit_count = rec[0];
+        best_on_host = false;
         return ISOCON_OK;
     }
     // the hits a pass left on the device join the host list (before anything else writes to the device lists)
@@ -211,9 +282,15 @@ struct NNContext {
     bool fixed = false;            // NNParams::fixed
     bool dev_excluded(uint32_t q) const { return mask_exc && is_exc(q); }
     bool flags_dirty = false;      // a wide stage left its own query flags on the device
-    int upload_flags()
+    bool roles_uniform = false;    // 1-set, no is_converged: every entry is query and target
+    int upload_flags(bool fresh = false)
     {
         if (!n) return ISOCON_OK;
+        if (fresh && roles_uniform && !st->n_exc) {          // (nn_setup: nothing to send, both role arrays are constants)
+            ISO_HIP_CHECK(hipMemsetAsync(d_qf.p, 1, n, 0));
+            ISO_HIP_CHECK(hipMemsetAsync(d_tf.p, 1, n, 0));
+            return ISOCON_OK;
+        }
         if (!st->n_exc || !mask_exc) {
             ISO_HIP_CHECK(copy_h2d(d_qf.p, qflag.data(), n));
             ISO_HIP_CHECK(copy_h2d(d_tf.p, tflag.data(), n));
@@ -296,6 +373,7 @@ int nn_setup(NNContext &C, isocon_store *s, const uint8_t *is_converged, const u
     for (uint32_t i = 1; i < n; ++i)
         if (s->lens[i] < s->lens[i - 1]) { g_last_error = "nearest-neighbour entry points need a length-sorted store"; return ISOCON_E_ARG; }
     C.two_set = is_target != nullptr;
+    C.roles_uniform = !C.two_set && !is_converged;
     C.min_d = C.two_set ? 0 : 1;
     C.qflag.assign(n, 0);
     C.tflag.assign(n, 0);
@@ -329,7 +407,7 @@ int nn_setup(NNContext &C, isocon_store *s, const uint8_t *is_converged, const u
         (rc = C.d_stats.alloc(2 * (NN_COUNTER_SLOTS * 4 + 1) * 8)))
         return rc;
     clk.lap("setup: pool");
-    if ((rc = C.upload_flags())) return rc;
+    if ((rc = C.upload_flags(true))) return rc;
     clk.lap("setup: role flags");
     return ISOCON_OK;
 }

@@ -14,41 +14,72 @@ int nn_phase_b(NNContext &C, const QMap &Q)
 }
 
 
-// The same CSR computed on the device (nn_finalize.hpp) from hits and bounds that are in device memory: six small kernels, the CSR comes
-// back.  best_host = the same bounds on the host (for out_best).  Returns ISOCON_E_UNSUPPORTED when a row is too long for the per-thread
-// sort (the caller then uses the host routine).
+// blocking host waits of one entry point (isocon_nn_last_host_waits): counted from here to the end of the scope
+struct WaitScope {
+    isocon_store *s;
+    explicit WaitScope(isocon_store *st) : s(st) { g_host_waits = 0; }
+    ~WaitScope() { if (s) s->last_host_waits = g_host_waits; }
+};
+
+// The same CSR computed on the device (nn_finalize.hpp) from hits and bounds that are in device memory: seven small kernels, then one
+// 16-byte record (row too long?  how many columns?) and ONE download of row pointers, bounds and columns, which sit behind one another
+// in one buffer.  best_host = the same bounds on the host (for out_best), nullptr: they come back with the CSR.  Returns
+// ISOCON_E_UNSUPPORTED when a row is too long for the per-thread sort (the caller then uses the host routine).
 int nn_finalize_device_core(ScratchPool *pl, uint32_t n, const int32_t *d_best, const int32_t *best_host, const int32_t *d_hits, uint64_t n_hits,
                             int32_t *out_best, uint64_t *out_row_ptr, uint32_t *out_cols, uint64_t cols_cap, uint64_t *n_cols_needed)
 {
     DevBuf d_cnt(pl, SLOT_NN_FIN_CNT), d_start(pl, SLOT_NN_FIN_START), d_cur(pl, SLOT_NN_FIN_CUR), d_nb(pl, SLOT_NN_FIN_NB),
-        d_len2(pl, SLOT_NN_FIN_LEN2), d_rowptr(pl, SLOT_NN_FIN_ROWPTR), d_cols(pl, SLOT_NN_FIN_COLS), d_flag(pl, SLOT_NN_FIN_FLAG);
+        d_len2(pl, SLOT_NN_FIN_LEN2), d_out(pl, SLOT_NN_FIN_OUT), d_rec(pl, SLOT_NN_FIN_FLAG);
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "row pointers travel as they are");
+    // [row_ptr: n + 1][best: n, only when the host does not have it][cols: up to n_hits], each part at a 16-byte boundary
+    const size_t rp_bytes = (((size_t)n + 1) * 8 + 15) & ~(size_t)15, best_bytes = best_host ? 0 : ((size_t)n * 4 + 15) & ~(size_t)15;
+    const size_t cols_off = rp_bytes + best_bytes;
     int rc;
     if ((rc = d_cnt.alloc((size_t)n * 4)) || (rc = d_start.alloc(((size_t)n + 1) * 8)) || (rc = d_cur.alloc((size_t)n * 4)) ||
-        (rc = d_nb.alloc((size_t)n_hits * 4 + 16)) || (rc = d_len2.alloc((size_t)n * 4)) || (rc = d_rowptr.alloc(((size_t)n + 1) * 8)) ||
-        (rc = d_cols.alloc((size_t)n_hits * 4 + 16)) || (rc = d_flag.alloc(4)))
+        (rc = d_nb.alloc((size_t)n_hits * 4 + 16)) || (rc = d_len2.alloc((size_t)n * 4)) || (rc = d_out.alloc(cols_off + (size_t)n_hits * 4 + 16)) ||
+        (rc = d_rec.alloc(16)))
         return rc;
+    unsigned long long *d_rowptr = d_out.as<unsigned long long>();
+    int32_t *d_best_out = best_host ? nullptr : reinterpret_cast<int32_t *>(d_out.as<char>() + rp_bytes);
+    uint32_t *d_cols = reinterpret_cast<uint32_t *>(d_out.as<char>() + cols_off);
     ISO_HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, (size_t)n * 4, 0));
     ISO_HIP_CHECK(hipMemsetAsync(d_cur.p, 0, (size_t)n * 4, 0));
-    ISO_HIP_CHECK(hipMemsetAsync(d_flag.p, 0, 4, 0));
+    ISO_HIP_CHECK(hipMemsetAsync(d_rec.p, 0, 16, 0));
     const unsigned hb = (unsigned)std::max<uint64_t>(1, (n_hits + 255) / 256), nb_ = (n + 255) / 256;
     hipLaunchKernelGGL(k_fin_count, dim3(hb), dim3(256), 0, 0, d_hits, (unsigned long long)n_hits, d_best, n, d_cnt.as<uint32_t>());
     if ((rc = device_exscan<0, unsigned long long>(pl, d_cnt.as<uint32_t>(), n, d_start.as<unsigned long long>()))) return rc;
     hipLaunchKernelGGL(k_fin_scatter, dim3(hb), dim3(256), 0, 0, d_hits, (unsigned long long)n_hits, d_best, n,
                        d_start.as<unsigned long long>(), d_cur.as<uint32_t>(), d_nb.as<uint32_t>());
-    hipLaunchKernelGGL(k_fin_rows, dim3(nb_), dim3(256), 0, 0, n, d_start.as<unsigned long long>(), d_nb.as<uint32_t>(), d_len2.as<uint32_t>(), d_flag.as<uint32_t>());
-    if ((rc = device_exscan<0, unsigned long long>(pl, d_len2.as<uint32_t>(), n, d_rowptr.as<unsigned long long>()))) return rc;
-    hipLaunchKernelGGL(k_fin_gather, dim3(nb_), dim3(256), 0, 0, n, d_start.as<unsigned long long>(), d_nb.as<uint32_t>(), d_rowptr.as<unsigned long long>(), d_cols.as<uint32_t>());
+    hipLaunchKernelGGL(k_fin_rows, dim3(nb_), dim3(256), 0, 0, n, d_start.as<unsigned long long>(), d_nb.as<uint32_t>(), d_len2.as<uint32_t>(), d_rec.as<uint32_t>());
+    if ((rc = device_exscan<0, unsigned long long>(pl, d_len2.as<uint32_t>(), n, d_rowptr))) return rc;
+    hipLaunchKernelGGL(k_fin_gather, dim3(nb_), dim3(256), 0, 0, n, d_start.as<unsigned long long>(), d_nb.as<uint32_t>(), d_rowptr, d_cols);
+    hipLaunchKernelGGL(k_fin_pack, dim3(std::max(1u, nb_)), dim3(256), 0, 0, n, d_rowptr, d_rec.as<unsigned long long>(), d_best, d_best_out);
     ISO_HIP_CHECK(hipGetLastError());
-    uint32_t flag = 0;
-    ISO_HIP_CHECK(hipMemcpy(&flag, d_flag.p, 4, hipMemcpyDeviceToHost));
-    if (flag) return ISOCON_E_UNSUPPORTED;
-    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "row pointers travel as they are");
-    ISO_HIP_CHECK(copy_d2h(out_row_ptr, d_rowptr.p, ((size_t)n + 1) * 8));
-    const uint64_t total = out_row_ptr[n];
+    unsigned long long rec[2] = {0, 0};          // {row too long (low word), columns}
+    ISO_HIP_CHECK(memcpy_wait(rec, d_rec.p, sizeof(rec), hipMemcpyDeviceToHost));
+    if (rec[0]) return ISOCON_E_UNSUPPORTED;
+    const uint64_t total = rec[1];
     if (n_cols_needed) *n_cols_needed = total;
     if (total > cols_cap) return ISOCON_E_CAPACITY;
-    if (total) ISO_HIP_CHECK(copy_d2h(out_cols, d_cols.p, (size_t)total * 4));
-    for (uint32_t i = 0; i < n; ++i) out_best[i] = out_row_ptr[i + 1] > out_row_ptr[i] ? best_host[i] : -1;
+    const size_t bytes = cols_off + (size_t)total * 4;
+    char *stg = bytes <= kStageBytes ? static_cast<char *>(g_stage.get(kStageBytes)) : nullptr;
+    const int32_t *best_src = best_host;
+    std::vector<int32_t> best_tmp;
+    if (stg) {
+        ISO_HIP_CHECK(memcpy_wait(stg, d_out.p, bytes, hipMemcpyDeviceToHost));
+        memcpy(out_row_ptr, stg, ((size_t)n + 1) * 8);
+        if (total) memcpy(out_cols, stg + cols_off, (size_t)total * 4);
+        if (!best_src) best_src = reinterpret_cast<const int32_t *>(stg + rp_bytes);
+    } else {          // larger than the staging buffer (or none): part by part
+        ISO_HIP_CHECK(copy_d2h(out_row_ptr, d_rowptr, ((size_t)n + 1) * 8));
+        if (total) ISO_HIP_CHECK(copy_d2h(out_cols, d_cols, (size_t)total * 4));
+        if (!best_src) {
+            best_tmp.resize(std::max<uint32_t>(n, 1));
+            if (n) ISO_HIP_CHECK(copy_d2h(best_tmp.data(), d_best_out, (size_t)n * 4));
+            best_src = best_tmp.data();
+        }
+    }
+    for (uint32_t i = 0; i < n; ++i) out_best[i] = out_row_ptr[i + 1] > out_row_ptr[i] ? best_src[i] : -1;
     return ISOCON_OK;
 }
 
@@ -80,12 +111,14 @@ extern "C" int isocon_nn_partial(isocon_store *s, const uint8_t *is_converged, c
     const uint32_t n = s->dev.n;
     if (q_end > n) q_end = n;
     const QMap Q = qmap_of(q_begin, q_end, q_stride, q_block);
+    WaitScope waits(s);
     NNContext C;
     int rc = nn_setup(C, s, is_converged, is_target, depth, best_inout);
     if (rc) return rc;
     if (phase == 2 && wide_queries) C.wide_mask.assign(wide_queries, wide_queries + n);
     rc = phase == 2 ? nn_phase_b(C, Q) : nn_phase_a(C, Q, false, phase == 0 || phase == 3, phase == 1 || phase == 3, phase == 1);
     if (rc) return rc;
+    C.tm.resolve();
     C.stats.kernel_ms = C.tm.total; C.stats.narrow_kernel_ms = C.tm.marked_total;
     if (stats) *stats = C.stats;
     std::copy(C.best.begin(), C.best.begin() + n, best_inout);
@@ -112,6 +145,7 @@ extern "C" int isocon_nn_partial_dev(isocon_store *s, const uint8_t *is_converge
     const uint32_t n = s->dev.n;
     if (q_end > n) q_end = n;
     const QMap Q = qmap_of(q_begin, q_end, q_stride, q_block);
+    WaitScope waits(s);
     std::vector<int32_t> best(std::max<uint32_t>(n, 1), NN_INF);
     if (n) ISO_HIP_CHECK(copy_d2h(best.data(), best_inout_dev, (size_t)n * 4));
     NNContext C;
@@ -121,6 +155,7 @@ extern "C" int isocon_nn_partial_dev(isocon_store *s, const uint8_t *is_converge
     C.keep_dev = phase != 2;          // the main pass' hits go from its device list to the held list without visiting the host
     rc = phase == 2 ? nn_phase_b(C, Q) : nn_phase_a(C, Q, false, phase == 0 || phase == 3, phase == 1 || phase == 3, phase == 1);
     if (rc) return rc;
+    C.tm.resolve();
     C.stats.kernel_ms = C.tm.total; C.stats.narrow_kernel_ms = C.tm.marked_total;
     if (stats) *stats = C.stats;
     if (n) ISO_HIP_CHECK(copy_h2d(best_inout_dev, C.best.data(), (size_t)n * 4));
@@ -131,13 +166,13 @@ extern "C" int isocon_nn_partial_dev(isocon_store *s, const uint8_t *is_converge
         void *bigger = nullptr;
         const size_t want = (size_t)(have + add) * 12 * 2 + ((size_t)1 << 20);
         ISO_HIP_CHECK(hipMalloc(&bigger, want));
-        if (have) ISO_HIP_CHECK(hipMemcpy(bigger, slot.p, (size_t)have * 12, hipMemcpyDeviceToDevice));
+        if (have) ISO_HIP_CHECK(memcpy_wait(bigger, slot.p, (size_t)have * 12, hipMemcpyDeviceToDevice));
         if (slot.p) (void)hipFree(slot.p);
         slot.p = bigger; slot.cap = want;
     }
     if (add_host) ISO_HIP_CHECK(copy_h2d(static_cast<char *>(slot.p) + (size_t)have * 12, C.hits.data(), (size_t)add_host * 12));
     if (C.dev_hit_count)
-        ISO_HIP_CHECK(hipMemcpy(static_cast<char *>(slot.p) + (size_t)(have + add_host) * 12, C.dev_hits, (size_t)C.dev_hit_count * 12, hipMemcpyDeviceToDevice));
+        ISO_HIP_CHECK(memcpy_wait(static_cast<char *>(slot.p) + (size_t)(have + add_host) * 12, C.dev_hits, (size_t)C.dev_hit_count * 12, hipMemcpyDeviceToDevice));
     s->pool.held_hits.rows = have + add;
     *n_hits_held = s->pool.held_hits.rows;
     return ISOCON_OK;
@@ -160,7 +195,7 @@ extern "C" int isocon_nn_hits_dev(isocon_store *s, const int32_t *best_dev, int3
         hipLaunchKernelGGL(k_filter_hits, dim3(blocks), dim3(256), 0, 0, static_cast<const int32_t *>(s->pool.slots[SLOT_NN_ACC_HITS].p), (unsigned long long)rows,
                            best_dev, out_hits_dev, d_c.as<unsigned long long>());
         ISO_HIP_CHECK(hipGetLastError());
-        if (n_kept) ISO_HIP_CHECK(hipMemcpy(&kept, d_c.p, 8, hipMemcpyDeviceToHost));
+        if (n_kept) ISO_HIP_CHECK(memcpy_wait(&kept, d_c.p, 8, hipMemcpyDeviceToHost));
     }
     if (n_kept) *n_kept = kept;
     return ISOCON_OK;
@@ -191,6 +226,7 @@ extern "C" int isocon_nn_graph(isocon_store *s, const uint8_t *is_converged, con
     if (getenv("ISOCON_DEBUG")) { (void)hipDeviceSynchronize(); clk0.lap("sync at entry"); }
     struct Total { std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
                    ~Total() { if (getenv("ISOCON_DEBUG")) fprintf(stderr, "[isocon] %-28s %8.2f ms\n", "isocon_nn_graph total", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count()); } } total;
+    WaitScope waits(s);
     NNContext C;
     int rc = nn_setup(C, s, is_converged, is_target, depth, nullptr, true);
     if (rc) return rc;
@@ -199,28 +235,34 @@ extern "C" int isocon_nn_graph(isocon_store *s, const uint8_t *is_converged, con
     // 2-set with a depth limit that binds: the order-dependent rule of NNG:416, round by round (ISOCON_DEBUG_VARIANT=nn_2set_walk: every 2-set call)
     if (C.two_set && (C.depth_binds || variant("nn_2set_walk"))) return nn2_depth_graph(C, depth, out_best, out_row_ptr, out_cols, cols_cap, n_cols_needed, stats);
     C.keep_dev = n >= 1024 && !variant("nn_host_finalize");
+    C.csr_follows = C.keep_dev;          // the ordinary case ends the 64-row phase with one record: hits and bounds stay on the device for the CSR kernels
+    C.fill_best = !s->n_exc;             // no bounds from the caller: best[] starts as a fill on the device
     if ((rc = nn_phase_a(C, QMap{0u, n, 1u, 0u}, true, true, true))) return rc;
     HostClock clk;
-    C.keep_dev = false;
-    if (C.dev_hit_count) {
-        // Phase B appends to the device list from its start again (and may re-allocate it): if it is going to run -- an entry still
-        // without a neighbour that the 64-row pass could not have resolved -- phase A's hits leave the device first.
-        bool wide = false;
-        for (uint32_t q = 0; q < n && !wide; ++q) wide = C.qflag[q] && C.best[q] == NN_INF && s->lens[q] > 63;
-        if (wide && (rc = C.pull_dev_hits())) return rc;
+    C.keep_dev = C.csr_follows = C.fill_best = false;
+    bool run_b = true;
+    if (!C.best_on_host) {
+        // Phase A left hits and bounds on the device and said whether phase B is going to run -- an entry still without a neighbour that
+        // the 64-row pass could not have resolved.  Phase B works on the host's bounds and appends to the device list from its start
+        // again (and may re-allocate it): then both leave the device first.  Nothing to build a CSR from: the host routine takes over.
+        if (C.wide_needed || !C.dev_hit_count) {
+            if ((rc = C.download_best()) || (rc = C.pull_dev_hits())) return rc;
+        } else run_b = false;
     }
-    if ((rc = nn_phase_b(C, QMap{0u, n, 1u, 0u}))) return rc;
+    if (run_b && (rc = nn_phase_b(C, QMap{0u, n, 1u, 0u}))) return rc;
     clk.lap("phaseB");
+    C.tm.resolve();
     if (C.dev_hit_count) {
         // phase A left its hits on the device.  Nothing came after it (the ordinary case): the CSR is built from them where they are.
         if (C.hits.empty()) {
             C.stats.kernel_ms = C.tm.total; C.stats.narrow_kernel_ms = C.tm.marked_total;
             if (stats) *stats = C.stats;
-            rc = nn_finalize_device_core(&s->pool, n, C.d_best.as<int32_t>(), C.best.data(), C.dev_hits, C.dev_hit_count, out_best, out_row_ptr, out_cols, cols_cap, n_cols_needed);
+            rc = nn_finalize_device_core(&s->pool, n, C.d_best.as<int32_t>(), C.best_on_host ? C.best.data() : nullptr, C.dev_hits, C.dev_hit_count, out_best, out_row_ptr, out_cols, cols_cap, n_cols_needed);
             clk.lap("finalize (device hits)");
             if (rc != ISOCON_E_UNSUPPORTED && rc != ISOCON_E_HIP) return rc;
         }
-        // ... otherwise (wide bands found more, or a row too long for the device sort) they join the host list
+        // ... otherwise (a row too long for the device sort) they join the host list, and the bounds the host's
+        if (!C.best_on_host && (rc = C.download_best())) return rc;
         if ((rc = C.pull_dev_hits())) return rc;
     }
     C.stats.kernel_ms = C.tm.total; C.stats.narrow_kernel_ms = C.tm.marked_total;
@@ -250,7 +292,8 @@ extern "C" int isocon_qgram_bound_matrix(isocon_store *s, uint32_t q_begin, uint
     const QMap Q = qmap_of(q_begin, q_end, q_stride, q_block);
     const uint32_t nq = Q.count();
     if ((rc = C.build_bounds(Q, 63, P))) return rc;
-    ISO_HIP_CHECK(hipDeviceSynchronize());
+    ISO_HIP_CHECK(device_wait());
+    C.tm.resolve();
     s->pool.bound_tag.valid = false;
     uint64_t total = 0;
     if (P.lb == nullptr) {          // no pair inside the window (or no room for the matrix)

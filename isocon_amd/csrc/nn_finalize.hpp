@@ -70,4 +70,30 @@ __global__ __launch_bounds__(256) void k_fin_gather(uint32_t n, const unsigned l
     for (uint32_t a = 0; a < len; ++a) dst[a] = src[a];
 }
 
+// What the host needs of the CSR before it fetches it, next to the "row too long" flag k_fin_rows left in rec[0]: rec[1] = number of
+// columns.  best_out != nullptr: the bounds travel with the CSR (a copy behind the row pointers, one download for all three).
+__global__ __launch_bounds__(256) void k_fin_pack(uint32_t n, const unsigned long long *__restrict__ row_ptr, unsigned long long *__restrict__ rec,
+                                                   const int32_t *__restrict__ best, int32_t *__restrict__ best_out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i == 0) rec[1] = row_ptr[n];
+    if (best_out != nullptr && i < n) best_out[i] = best[i];
+}
+
+// What the host needs of the 64-row phase before the CSR kernels, as one record: rec[0] = hits recorded, rec[1] = 1 if an entry that acts
+// as a query is still without a neighbour and longer than 63 (the wide-band phase has to run), rec[2 ..] = the n_stats counters.
+// rec[1] is zero at launch.
+__global__ __launch_bounds__(256) void k_nn_step_record(const unsigned long long *__restrict__ hit_count, const unsigned long long *__restrict__ stats, uint32_t n_stats,
+                                                         const int32_t *__restrict__ best, const uint8_t *__restrict__ qflag, const int32_t *__restrict__ lens,
+                                                         uint32_t n, unsigned long long *__restrict__ rec)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (blockIdx.x == 0) {
+        if (threadIdx.x == 0) rec[0] = *hit_count;
+        for (uint32_t k = threadIdx.x; k < n_stats; k += 256u) rec[2 + k] = stats[k];
+    }
+    const bool wide = i < n && qflag[i] != 0 && best[i] == NN_INF && lens[i] > 63;
+    if (__ballot(wide) != 0 && (threadIdx.x & 63u) == 0) atomicOr(rec + 1, 1ull);
+}
+
 }  // namespace isocon

@@ -16,8 +16,8 @@ int NNContext::plan_lists(const QMap &Q, uint32_t nq, const NNParams &PR, ListPl
     if (const char *e = variant_value("nn_list_min")) list_min = (uint32_t)std::max(1, atoi(e));        // A/B runs
     const uint32_t build_min = filter ? std::min<uint32_t>(list_min, NNF_LIST_MIN) : list_min;
     const unsigned long long cap_in = pairs_cap / build_min + 1, cap_out = filter ? pairs_cap / list_min + 1 : cap_in;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || pairs_cap * 12 > free_b / 2 + st->pool.slots[SLOT_NN_LIST].cap * 3) return ISOCON_OK;
+    size_t free_b = 0;
+    if (!free_mem(free_b) || pairs_cap * 12 > free_b / 2 + st->pool.slots[SLOT_NN_LIST].cap * 3) return ISOCON_OK;
     DevBuf *bufs[] = {&d_ltot, &d_lchunks, &d_list, &d_lpa, &d_lpb, &d_lmeta, &d_ltasks};
     const int slots[] = {SLOT_NN_LTOT, SLOT_NN_LCHUNKS, SLOT_NN_LIST, SLOT_NN_LPA, SLOT_NN_LPB, SLOT_NN_LDEST, SLOT_NN_LTASKS};
     for (int i = 0; i < 7; ++i) { bufs[i]->pool = &st->pool; bufs[i]->slot = slots[i]; }
@@ -64,12 +64,11 @@ int NNContext::plan_lists(const QMap &Q, uint32_t nq, const NNParams &PR, ListPl
             ISO_HIP_CHECK(hipGetLastError());
         }
     }
+    tm.stop_later(&stats.list_kernel_ms, &stats.filter_kernel_ms);          // (the filter's part of list_kernel_ms; the context's own marked time is narrow_kernel_ms)
+    // (the interval closes in front of the copy of the totals, not behind it as it used to: list_kernel_ms is the kernels' time alone)
+    // the one answer the host cannot go on without: how many chunks and pairs the filter left decides which launches follow
     NNPlanTotals tot;
-    ISO_HIP_CHECK(hipMemcpy(&tot, d_ltot.p, sizeof(tot), hipMemcpyDeviceToHost));
-    const float before = tm.marked_total;
-    stats.list_kernel_ms += tm.stop();
-    stats.filter_kernel_ms += tm.marked_total - before;          // (part of list_kernel_ms)
-    tm.marked_total = before;          // (the context's marked time is the narrow table launch's: narrow_kernel_ms)
+    ISO_HIP_CHECK(memcpy_wait(&tot, d_ltot.p, sizeof(tot), hipMemcpyDeviceToHost));
     if (tot.overflow) return ISOCON_OK;      // the bounds reject too little: lists would not fit
     stats.pairs_prefiltered += tot.n_filtered;
     stats.pairs_block_rejected += tot.f_rejected + tot.f_rejected2;

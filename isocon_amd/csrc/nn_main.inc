@@ -55,7 +55,7 @@ int nn_phase_a_planes(NNContext &C, const QMap &Q, bool allow_regroup = false,
                     C.tm.start();
                     hipLaunchKernelGGL(k_nn_scan_up<1>, dim3((nq + 3) / 4), dim3(256), 0, 0, C.st->dev, C.params(63), Q, 0, 1, 1);
                     ISO_HIP_CHECK(hipGetLastError());
-                    C.stats.seed_kernel_ms += C.tm.stop();
+                    C.tm.stop_later(&C.stats.seed_kernel_ms);
                     clk.lap("phaseA: seed kernel");
                 }
             }
@@ -144,7 +144,7 @@ int nn_phase_a_planes(NNContext &C, const QMap &Q, bool allow_regroup = false,
                 const size_t ring8 = 8 * NN_RING * 8 + 16, ring16 = 16 * NN_RING * 8 + 16, cu_lds = 160 * 1024;
                 if (n >= (1u << 30)) { g_last_error = "store too large for the packed neighbour queue"; return ISOCON_E_ARG; }
                 bool refill = !tiles_kernel && lds_r + ring16 <= cu_lds && perm.empty();
-                if (refill) refill = C.ensure_text();          // lane texts as nibbles, one fixed-stride row per sequence
+                if (refill) refill = C.text_affordable();          // lane texts as nibbles, one fixed-stride row per sequence: room now, built in front of the first launch that reads them
                 const uint32_t text_stride = C.text_stride;
                 DevBuf &d_il_text = C.d_text;
                 if (!refill && lds <= 160 * 1024) {  // lane texts with interleaved code bits (of the regrouped copy, if any)
@@ -155,7 +155,7 @@ int nn_phase_a_planes(NNContext &C, const QMap &Q, bool allow_regroup = false,
                 }
                 if (refill && bounds_wanted && !bounds_built) {
                     // q-gram bounds of every pair of the pass (outside the main kernel's own event pair: bound_kernel_ms)
-                    ms += C.tm.stop();
+                    C.tm.stop_later(&C.stats.scan_kernel_ms);
                     if ((rc = C.build_bounds(Q, 63, PR))) return rc;
                     clk.lap("phaseA: q-gram bounds");
                     C.tm.start();
@@ -169,12 +169,13 @@ int nn_phase_a_planes(NNContext &C, const QMap &Q, bool allow_regroup = false,
                 NNContext::ListPlan LP;
                 if (refill && PR.lb != nullptr) {
                     // the survivors of the bounds as lists, through the block filter: tables only for entries with enough pairs, and only their pairs
-                    ms += C.tm.stop();
+                    C.tm.stop_later(&C.stats.scan_kernel_ms);
                     if ((rc = C.plan_lists(Q, nq, PR, LP))) return rc;
                     clk.lap("phaseA: survivor lists");
                     C.tm.start();
                 }
                 const bool listed = LP.listed;
+                if (refill && !listed && !C.build_text()) return ISOCON_E_HIP;          // every launch of the chain below reads the text
                 const unsigned long long n_chunks = LP.n_chunks, n_chunks_narrow = LP.n_chunks_narrow, n_small = LP.n_small + LP.conv_pairs;
                 no_markers = listed && seeds_clean;
                 if (listed) {
@@ -186,6 +187,7 @@ int nn_phase_a_planes(NNContext &C, const QMap &Q, bool allow_regroup = false,
                     // and residency is not what binds the launch -- DESIGN 4.4), 8 for the 32-row class (0.86 against 0.94 ms); nn_list_waves= overrides both
                     const char *lw = variant_value("nn_list_waves");
                     const int lw64 = lw ? atoi(lw) : 4, lw32 = lw ? atoi(lw) : 8;
+                    if ((n_chunks || n_chunks_narrow) && !C.build_text()) return ISOCON_E_HIP;
                     if (n_chunks) {
                         // the 64-row class; largest chunks first (the sorted tables sit behind the unsorted ones)
                         NNChunk *sorted = LP.sorted_a;
@@ -228,7 +230,7 @@ int nn_phase_a_planes(NNContext &C, const QMap &Q, bool allow_regroup = false,
                         PL.stats = C.d_stats.as<unsigned long long>();
                     }
                     if (n_small) {
-                        ms += C.tm.stop();
+                        C.tm.stop_later(&C.stats.scan_kernel_ms);
                         C.tm.start();
                         const unsigned long long pairs_cap = C.st->pool.slots[SLOT_NN_LPA].cap / 4;
                         if (LP.conv_a) hipLaunchKernelGGL(k_nn_chunks_to_pairs, dim3((unsigned)LP.conv_a), dim3(256), 0, 0, LP.a, C.d_list.as<uint32_t>(), C.d_lpa.as<uint32_t>(), C.d_lpb.as<uint32_t>(), pairs_cap, C.d_ltot.as<NNPlanTotals>());
@@ -236,7 +238,7 @@ int nn_phase_a_planes(NNContext &C, const QMap &Q, bool allow_regroup = false,
                         hipLaunchKernelGGL(k_ed_lanes<true>, dim3((unsigned)((n_small + 255) / 256)), dim3(256), 0, 0, C.st->dev, C.params(63), C.d_lpa.as<uint32_t>(), C.d_lpb.as<uint32_t>(),
                                            (const int32_t *)nullptr, (uint64_t)n_small, (int32_t *)nullptr);
                         ISO_HIP_CHECK(hipGetLastError());
-                        C.stats.lanes_kernel_ms += C.tm.stop();
+                        C.tm.stop_later(&C.stats.lanes_kernel_ms);
                         C.stats.pairs_evaluated += n_small;
                         C.stats.pairs_lanes += n_small;
                         C.tm.start();
@@ -257,7 +259,7 @@ int nn_phase_a_planes(NNContext &C, const QMap &Q, bool allow_regroup = false,
                     hipLaunchKernelGGL(k_nn_scan_up<1>, dim3(nq), dim3(256), 0, 0, S, C.params(63), Q, first_tile, 0x7fffffff, 4);
                 }
                 ISO_HIP_CHECK(hipGetLastError());
-                ms += C.tm.stop();
+                C.tm.stop_later(&C.stats.scan_kernel_ms);
                 C.stats.scan_launches += 1;
             }
             if (!do_main) no_markers = do_seed && seeds_clean;          // a seed-only phase: k_ed_lanes alone
@@ -265,7 +267,7 @@ int nn_phase_a_planes(NNContext &C, const QMap &Q, bool allow_regroup = false,
             clk.lap("phaseA: main kernel");
         } else if (do_main && !variant("nn_tiles") && n < (1u << 30) &&
                    (size_t)std::count(C.tflag.begin(), C.tflag.end(), (uint8_t)1) > 512 &&      // few candidates: explicit tiles are cheaper than a table per entry
-                   ((size_t)4 * ((C.st->maxlen + 192 + 31) & ~31) + 160) * 4 + 16 * NN_RING * 8 + 16 <= (size_t)160 * 1024 && C.ensure_text()) {
+                   ((size_t)4 * ((C.st->maxlen + 192 + 31) & ~31) + 160) * 4 + 16 * NN_RING * 8 + 16 <= (size_t)160 * 1024 && C.text_affordable()) {
             // reads vs candidates with the same upward scan as the 1-set search: the role flags make a pair admissible
             // only if one end is a read and the other a candidate; the pair belongs to its LOWER index, whatever its role
             const uint32_t nq = Q.count();
@@ -273,6 +275,7 @@ int nn_phase_a_planes(NNContext &C, const QMap &Q, bool allow_regroup = false,
             NNParams PR = C.params(63);
             if ((rc = C.build_bounds(Q, 63, PR))) return rc;
             C.tm.start();
+            if (!C.build_text()) return ISOCON_E_HIP;
             if (3 * (lds_r + ring8) <= (size_t)160 * 1024) {
                 hipLaunchKernelGGL((k_nn_scan_refill<8, 1>), dim3(nq), dim3(512), lds_r, 0, C.st->dev, PR, C.d_text.as<uint32_t>(), C.text_stride,
                                    Q, 0);
@@ -282,7 +285,7 @@ int nn_phase_a_planes(NNContext &C, const QMap &Q, bool allow_regroup = false,
                                    Q, 0);
             }
             ISO_HIP_CHECK(hipGetLastError());
-            ms += C.tm.stop();
+            C.tm.stop_later(&C.stats.scan_kernel_ms);
             C.stats.scan_launches += 1;
         } else {
             // (fallback: sequences too long for the LDS planes)  shared = candidate, lanes = the shard's reads whose
@@ -307,7 +310,9 @@ int nn_phase_a_planes(NNContext &C, const QMap &Q, bool allow_regroup = false,
         std::vector<int32_t> got;
         // single-GPU graph, ordinary case: the hits stay on the device for the CSR kernels (nn_finalize.hpp); nothing to post-process
         const bool dev_ok = C.keep_dev && no_markers && perm_used.empty() && !seed_collected && C.hits.empty();
-        rc = C.collect(got, &needed, perm_used.empty(), dev_ok);    // (a regrouped run keeps best[] in permuted positions: no filter)
+        const bool one_record = dev_ok && C.csr_follows && !C.st->n_exc && !C.flags_dirty;          // (the record reads the device's query flags: they must be the context's)
+        rc = one_record ? C.collect_record(&needed) : C.collect(got, &needed, perm_used.empty(), dev_ok);    // (a regrouped run keeps best[] in permuted positions: no filter)
+        C.tm.resolve();          // (behind the wait of the collect: the events are all reached)
         if (rc == ISOCON_E_CAPACITY) {   // the hit list overflowed: run again with a larger one
             C.hits_cap = needed + needed / 2 + 1024;
             if ((rc = C.d_hits.alloc(C.hits_cap * 12))) return rc;
@@ -323,6 +328,7 @@ int nn_phase_a_planes(NNContext &C, const QMap &Q, bool allow_regroup = false,
             continue;
         }
         if (rc) return rc;
+        if (one_record) { clk.lap("phaseA: hits and bounds stay on the device"); return ISOCON_OK; }
         if ((rc = C.download_best())) return rc;
         if (dev_ok) { clk.lap("phaseA: hits stay on the device"); return ISOCON_OK; }
         if (!perm_used.empty()) {           // back to the caller's positions
