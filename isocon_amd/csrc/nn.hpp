@@ -12,6 +12,7 @@
 //     arg-min set of x is { hits of x with d == final best[x] }.
 #pragma once
 #include "ed_band.hpp"
+#include "nn_scan_shape.hpp"
 
 namespace isocon {
 
@@ -260,7 +261,7 @@ __global__ __launch_bounds__(256) void k_filter_hits(const int32_t *__restrict__
 // when the launch comes with them, the pair's q-gram lower bound <= threshold: qgram.hpp) with coalesced loads, and queued
 // in a small per-wave ring in LDS.  With the bounds the host launches 4 waves per table instead of 8 (nn_main.inc) and may
 // hand the workgroups their entries widest window first (P.slot_order).
-static constexpr int NN_RING = 96;       // entries per wave (8 B each)
+// (NN_RING, the entries of a wave's ring, 8 B each: nn_scan_shape.hpp, with the launch shapes that depend on it)
 static constexpr int NN_TEXT_PAD_FRONT = 4, NN_TEXT_PAD_BACK = 6;     // dwords around each sequence of the nibble store
 
 struct __attribute__((packed, aligned(4))) TextQuad { uint32_t x, y, z, w; };

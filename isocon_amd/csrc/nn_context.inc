@@ -1,11 +1,16 @@
 // nn_context.inc -- state and helpers of the nearest-neighbour search on the host (first of the nn_*.inc pieces included by isocon_hip.hip:
 // nn_context / nn_bounds / nn_lists / nn_main / nn_wide / nn_images / nn_entry -- one translation unit, split by phase).
 //
-// Phase A: every admissible pair within |len difference| <= 63 through the 64-row band (kernel k_nn_scan_up for
-//          the 1-set graph, explicit tiles with the candidate as the shared sequence for the 2-set graph).
-// Phase B: queries that still have no neighbour (NN distance > 63): 128/256/512-row bands over their whole
-//          admissible window, then the un-banded kernel with k = len(query)
-//          (/root/reference/modules/nearest_neighbor_graph.py:129 "best_ed = len(seq1)").
+// Phase A (nn_main.inc): every admissible pair within |len difference| <= 63 through the 64-row band.  Ordinarily: q-gram bounds of every
+//          pair of the pass (k_qgram_mm), the pairs with the smallest bounds aligned first as seeds (k_ed_lanes), the survivors of the
+//          bounds as lists through the block filter, then 64-row and 32-row table launches (k_nn_scan_refill) for the entries with
+//          enough pairs and one pair per lane (k_ed_lanes) for the rest.  Reads against many candidates (2-set) go the same way.
+//          Fallbacks: the refill kernel by its own admission when bounds or lists are not affordable; k_nn_scan_lds / k_nn_scan_up
+//          when its table does not fit the LDS (or under nn_tiles); explicit tiles (k_nn_tiles, the candidate as the shared sequence)
+//          for reads against few candidates.
+// Phase B (nn_wide.inc): queries that still have no neighbour (NN distance > 63): 128- to 512-row bands over their whole admissible
+//          window, the band chosen from a sample, then the un-banded kernel with k = len(query) (the reference's "best_ed = len(seq1)",
+//          modules/nearest_neighbor_graph.py:129).
 
 namespace {
 

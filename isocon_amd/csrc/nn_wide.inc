@@ -9,12 +9,13 @@ void launch_scan_wide(NNContext &C, const QMap &Q, int32_t kcap, const uint32_t 
 {
     const uint32_t nq = Q.count();
     // lane-refill kernel with the entry's match-mask planes in LDS when they fit, else the scalar-window scan
-    const size_t lds_w = ((size_t)4 * ((C.st->maxlen + 192 * W + 31) & ~31) + 128 * W + 32) * 4;
+    const size_t lds_w = nn_refill_lds(C.st->maxlen, 64 * W);
     // waves per workgroup: 16, but 12 for the 512-row form -- its column loop needs 131 registers, three more than a 1 024-thread workgroup
     // leaves a wave (they were 16 B of scratch around the refill path); at 768 threads the budget is 168
     constexpr int NW = W == 8 ? 12 : 16;
-    const size_t ring16 = NW * NN_RING * 8 + 16;
-    if (!variant("nn_tiles") && lds_w + ring16 <= (size_t)160 * 1024 && C.st->maxlen < 16384 && C.n < (1u << 30) && C.ensure_text()) {
+    // d_q_list != nullptr: the "sparse" launch of k_nn_scan_refill (nn.hpp) -- one workgroup per listed query instead of one per
+    // entry; pays when few entries act as queries (a workgroup per entry would run with one or two live lanes).
+    if (!variant("nn_tiles") && nn_refill_fits(C.st->maxlen, 64 * W, NW) && C.st->maxlen < 16384 && C.n < (1u << 30) && C.ensure_text()) {
         if (hipFuncSetAttribute((const void *)k_nn_scan_refill<NW, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w) == hipSuccess) {
             NNParams P = C.params(kcap);
             // A wide-band pass over many queries runs for seconds (C5, 200 000 reads, 384-row band: 45 s): it is issued as launches of at most
@@ -82,31 +83,9 @@ int nn_wide_stage(NNContext &C, const QMap &Q, int W, const std::vector<uint8_t>
         ISO_HIP_CHECK(hipGetLastError());
         const float wms = C.tm.stop();
         if (getenv("ISOCON_DEBUG")) fprintf(stderr, "[isocon] phaseB: %d-row band scan (%s%s), %zu queries: %.2f ms\n", 64 * W, what, sparse ? ", one workgroup per query" : "", count, wms);
-        uint64_t needed = 0;
-        std::vector<int32_t> got;
-        rc = C.collect(got, &needed, true);
-        if (rc == ISOCON_E_CAPACITY) {   // as in phase A: larger list, bounds kept
-            C.hits_cap = needed + needed / 2 + 1024;
-            if ((rc = C.d_hits.alloc(C.hits_cap * 12))) return rc;
-            if ((rc = C.download_best())) return rc;
-            continue;
-        }
-        if (rc) return rc;
-        if ((rc = C.download_best())) return rc;
-        std::vector<uint32_t> ra, rb;
-        for (size_t i = 0; i + 2 < got.size(); i += 3) {
-            if (got[i + 2] == -2) { ra.push_back((uint32_t)got[i]); rb.push_back((uint32_t)got[i + 1]); }
-            else { C.hits.push_back(got[i]); C.hits.push_back(got[i + 1]); C.hits.push_back(got[i + 2]); }
-        }
-        if (!ra.empty()) {
-            std::vector<int32_t> kk(ra.size(), kcap), dd(ra.size(), -1);
-            float ems = 0.f;
-            if ((rc = ed_pairs_impl(C.st, ra.data(), rb.data(), kk.data(), ra.size(), dd.data(), &ems, nullptr, C.image_pass))) return rc;
-            C.tm.total += ems;
-            for (size_t i = 0; i < ra.size(); ++i)
-                if (dd[i] >= 0) C.apply(ra[i], rb[i], dd[i]);
-        }
-        return ISOCON_OK;
+        bool again = false;
+        if ((rc = nn_end_pass(C, kcap, false, Regrouped(), nullptr, again))) return rc;          // (as in phase A: larger list, bounds kept)
+        if (!again) return ISOCON_OK;
     }
 }
 
@@ -219,7 +198,5 @@ int nn_phase_b_planes(NNContext &C, const QMap &Q)
     }
     return ISOCON_OK;
 }
-
-
 
 }  // namespace
