@@ -105,7 +105,7 @@ int NNContext::build_bounds(const QMap &Q, int32_t kcap, NNParams &P, bool want_
     d_lb.pool = d_lbrow.pool = d_lblen.pool = &st->pool;
     d_lb.slot = SLOT_NN_LB; d_lbrow.slot = SLOT_NN_LBROW; d_lblen.slot = SLOT_NN_LBLEN;
     int rc;
-    if ((rc = d_lb.alloc((size_t)total)) ||
+    if ((rc = d_lb.alloc((size_t)total + 16)) ||          // (16 spare bytes, as behind the transposed matrix: the list builder reads whole dwords at a row's end)
         (rc = d_lbrow.alloc((size_t)nq * 8)) || (rc = d_lblen.alloc((size_t)nq * 4)))
         return ISOCON_OK;          // no room: the pass runs without bounds
     d_lbt.pool = d_offT.pool = d_sloT.pool = d_lenT.pool = d_score.pool = &st->pool;

@@ -21,6 +21,7 @@
 // /root/reference/modules/nearest_neighbor_graph.py:136-178.
 #pragma once
 #include "nn.hpp"
+#include "nn_surv_core.hpp"
 
 namespace isocon {
 
@@ -68,10 +69,13 @@ struct NNBoundRows {
 __device__ __forceinline__ uint32_t nn_meta_len(uint32_t w) { return w & 0x3fffu; }
 __device__ __forceinline__ int32_t nn_meta_thr(uint32_t w) { return (int32_t)((w >> 14) & 0x7fu); }
 __device__ __forceinline__ uint32_t nn_meta_score(uint32_t w) { return w >> 23; }
+static constexpr uint32_t NN_META_PAD = 3;          // words behind the last entry's, all 0 (no roles: never a candidate): the scan loads four words at once
+typedef uint32_t NNMeta4 __attribute__((ext_vector_type(4), aligned(4)));          // four meta words of consecutive entries: one 16-byte load at a dword address
 
 __global__ __launch_bounds__(256) void k_nn_entry_meta(DevStore S, NNParams P, const uint32_t *__restrict__ score, uint32_t *__restrict__ meta, NNPlanTotals *__restrict__ totals)
 {
     const uint32_t x = blockIdx.x * 256u + threadIdx.x;
+    if (x >= S.n && x < S.n + NN_META_PAD) meta[x] = 0u;
     if (x < S.n) {
         const int32_t m = S.lens[x], b = load_relaxed_agent(P.best + x);
         int32_t thr = b < m ? b : m;
@@ -115,7 +119,6 @@ __global__ __launch_bounds__(64 * NN_SURV_WAVES) void k_nn_survivors(DevStore S,
     const int32_t m = (int32_t)nn_meta_len(mx);
     const int32_t kx0 = nn_meta_thr(mx);
     const uint32_t sx = nn_meta_score(mx);
-    const uint64_t lt_mask = ((uint64_t)1 << lane) - 1;
     uint32_t *st = stage[wave];
     // the staging buffer holds both classes: the 64-row class grows from its front (fill), the 32-row class from its back (fill_n)
     uint32_t fill = 0, fill_n = 0, filtered = 0, kept = 0;
@@ -140,72 +143,124 @@ __global__ __launch_bounds__(64 * NN_SURV_WAVES) void k_nn_survivors(DevStore S,
         if (!narrow_class) fill = 0;
     };
 #ifndef ISOCON_SURV_U
-#define ISOCON_SURV_U 8
+#define ISOCON_SURV_U 4
 #endif
-    constexpr int U = ISOCON_SURV_U;             // batches of 64 partners per iteration: their loads are independent
+    // batches of 256 row positions (nn_surv_core.hpp) per iteration: their loads are independent.  Four: 0.84 ms at C3 against 0.87 with two and
+    // 0.90 with eight; asking for the next iteration's loads ahead of the tests: 0.89 - 0.90 (profiles/surv_ab.txt; all before the stores were slimmed to 0.79)
+    constexpr int U = ISOCON_SURV_U;
+    const uint32_t q_block = Q.block();
+    const uint32_t role_mask = (x_isq ? 1u << 21 : 0u) | (x_ist ? 1u << 22 : 0u);          // the role bits of a partner that make a direction of the pair
+    // Q.entry() modulo 2^32 (entries are below 2^30)
+    auto entry_of = [&](uint32_t s) { return Q.begin + (s >> Q.block_log2) * Q.stride + (s & (q_block - 1u)); };
     // (the side is a compile-time constant of the loop body: own row = contiguous partners, transposed row = partners through the slot map)
     auto scan_side = [&](auto side_tag) {
         constexpr int side = decltype(side_tag)::value;
         const uint32_t len = side == 0 ? up_len : dn_len;
         const uint8_t *row = side == 0 ? B.lb + up_off : B.lbT + dn_off;
-        for (uint32_t c0 = 0; c0 < len; c0 += 64 * U) {
-            uint32_t y[U], lbv[U];
-            uint32_t my[U];
+        const uint32_t tail = (len - 1u) & ~3u;          // where the lanes behind the row's end read (all their positions are masked)
+        auto load_batches = [&](uint32_t c0, uint32_t (&lbv)[U], NNMeta4 (&my)[U]) {
+            // lane l: the positions e0 .. e0 + 3.  Their four bounds are one dword at any byte address (a row's storage is padded to 16-byte
+            // pieces and both matrices end with 16 spare bytes: nn_bounds.inc), their four meta words one 16-byte load at a dword address
+            // (meta has three words of padding) wherever the partners are consecutive entries.
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const uint32_t e = c0 + 64u * u + (uint32_t)lane;
-                const uint32_t ec = e < len ? e : len - 1;
-                y[u] = side == 0 ? x + 1u + ec : (uint32_t)Q.entry(dn_slo + ec);
-                my[u] = meta[y[u]];
-                lbv[u] = row[ec];
-            }
+                const uint32_t e0 = c0 + (uint32_t)SURV_BATCH * u + 4u * (uint32_t)lane;
+                const uint32_t ec = e0 < len ? e0 : tail;
+                __builtin_memcpy(&lbv[u], row + ec, 4);
+                if (side == 0) my[u] = *reinterpret_cast<const NNMeta4 *>(meta + (x + 1u + ec));
+                else {
+                    // four slots are four consecutive entries inside one block of the map (or when the map's blocks touch)
+                    const uint32_t s0 = dn_slo + ec;
+                    const bool apart = Q.stride != q_block && (s0 & (q_block - 1u)) + 3u >= q_block;
+                    if (__builtin_amdgcn_ballot_w64(apart) == 0) my[u] = *reinterpret_cast<const NNMeta4 *>(meta + entry_of(s0));
+                    else {
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (c0 + 64u * u >= len) break;                        // wave-uniform
-                const uint32_t e = c0 + 64u * u + (uint32_t)lane;
-                const bool inr = e < len;
-                const bool xq = inr && x_isq && (my[u] & (1u << 21));        // x queries y
-                const bool yq = inr && x_ist && (my[u] & (1u << 22));        // y queries x
-                int32_t kx = -1, ky = -1;
-                if (xq) kx = kx0;
-                if (yq) ky = nn_meta_thr(my[u]);
-                int32_t k = kx > ky ? kx : ky;
-                if (k > P.kcap) k = P.kcap;
-                const int32_t dl = m - (int32_t)nn_meta_len(my[u]), ad = dl < 0 ? -dl : dl;
-                const uint32_t sy_u = nn_meta_score(my[u]);
-                const bool cand = inr && k >= 0 && ad <= k;
-                const bool accept = cand && (int32_t)lbv[u] <= k;
-                // owner: larger hub score, ties to the lower index (side 0: x is the lower end)
-                const bool mine = accept && (side == 0 ? sy_u <= sx : sx > sy_u);
-                if (side == 0) { filtered += (uint32_t)__popcll(__ballot(cand && !accept)); kept += (uint32_t)__popcll(__ballot(accept)); }
-                // class mode +1: the pairs with a threshold above the 32-row form's go straight to the pair arrays
-                const bool wide = mine && class_mode > 0 && k > NN_NARROW_K;
-                const uint64_t wm = __ballot(wide);
-                if (wm != 0) {
-                    const int first = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(wm));
-                    unsigned long long wbase = 0;
-                    if (lane == first) {
-                        wbase = atomicAdd(&totals->n_small, (unsigned long long)__popcll(wm));
-                        atomicAdd(&totals->n_wide_pairs, (unsigned long long)__popcll(wm));
-                        if (wbase + (unsigned long long)__popcll(wm) > small_cap) { atomicOr(&totals->overflow, 1ull); wbase = ~0ull; }
-                    }
-                    wbase = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(wbase >> 32), first) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)wbase, first);
-                    if (wide && wbase != ~0ull) {
-                        const unsigned long long at = wbase + (unsigned long long)__popcll(wm & lt_mask);
-                        pa[at] = x; pb[at] = y[u];
+                        for (int b = 0; b < SURV_PER_LANE; ++b) my[u][b] = meta[entry_of(dn_slo + (ec + b < len ? ec + b : len - 1u))];
                     }
                 }
-                const bool keep = mine && !wide;
-                const bool to_narrow = keep && class_mode >= 0 && k <= NN_NARROW_K;
-                const uint64_t am = __ballot(keep && !to_narrow), an = __ballot(to_narrow);
-                if ((am | an) == 0) continue;                            // wave-uniform
-                const uint32_t word = y[u] | (xq ? 0x40000000u : 0u) | (yq ? 0x80000000u : 0u);
-                if (keep && !to_narrow) st[fill + (uint32_t)__popcll(am & lt_mask)] = word;
-                if (to_narrow) st[NN_STAGE - 1 - (fill_n + (uint32_t)__popcll(an & lt_mask))] = word;
-                fill += (uint32_t)__popcll(am);
-                fill_n += (uint32_t)__popcll(an);
-                if (fill + fill_n >= NN_LIST_CHUNK) emit_chunk(fill_n > fill);          // the buffer is full: its larger class leaves (>= half a chunk)
             }
+        };
+        auto scan_batches = [&](uint32_t c0, const uint32_t (&lbv)[U], const NNMeta4 (&my)[U]) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (c0 + (uint32_t)SURV_BATCH * u >= len) break;                        // wave-uniform
+                const uint32_t e0 = c0 + (uint32_t)SURV_BATCH * u + 4u * (uint32_t)lane;
+                uint64_t am[SURV_PER_LANE], an[SURV_PER_LANE], aw[SURV_PER_LANE];          // keep masks: 64-row class, 32-row class, pairs that leave for their threshold
+#pragma unroll
+                for (int b = 0; b < SURV_PER_LANE; ++b) {
+                    const uint32_t myb = my[u][b];
+                    const bool inr = e0 + b < len;
+                    const bool xq = inr && x_isq && (myb & (1u << 21));        // x queries y
+                    const bool yq = inr && x_ist && (myb & (1u << 22));        // y queries x
+                    int32_t kx = -1, ky = -1;
+                    if (xq) kx = kx0;
+                    if (yq) ky = nn_meta_thr(myb);
+                    int32_t k = kx > ky ? kx : ky;
+                    if (k > P.kcap) k = P.kcap;
+                    const int32_t dl = m - (int32_t)nn_meta_len(myb), ad = dl < 0 ? -dl : dl;
+                    const uint32_t sy_u = nn_meta_score(myb);
+                    const bool cand = inr && k >= 0 && ad <= k;
+                    const bool accept = cand && (int32_t)((lbv[u] >> (8 * b)) & 0xffu) <= k;
+                    // owner: larger hub score, ties to the lower index (side 0: x is the lower end)
+                    const bool mine = accept && (side == 0 ? sy_u <= sx : sx > sy_u);
+                    if (side == 0) { filtered += cand && !accept ? 1u : 0u; kept += accept ? 1u : 0u; }          // (per lane: summed once per entry)
+                    // class mode +1: the pairs with a threshold above the 32-row form's go straight to the pair arrays
+                    const bool wide = mine && class_mode > 0 && k > NN_NARROW_K;
+                    const bool keep = mine && !wide;
+                    const bool to_narrow = keep && class_mode >= 0 && k <= NN_NARROW_K;
+                    aw[b] = __builtin_amdgcn_ballot_w64(wide);
+                    am[b] = __builtin_amdgcn_ballot_w64(keep && !to_narrow);
+                    an[b] = __builtin_amdgcn_ballot_w64(to_narrow);
+                }
+                // (what a kept pair needs beyond its mask bit is made where it is stored: most batches keep nothing)
+                // the list word of pair b: partner | x queries y << 30 | y queries x << 31 (a kept pair is in range: its role bits are the meta word's)
+                const auto word = [&](int b) {
+                    const uint32_t y = side == 0 ? x + 1u + e0 + (uint32_t)b : entry_of(dn_slo + e0 + (uint32_t)b);
+                    return y | (my[u][b] & role_mask) << 9;
+                };
+                if (class_mode > 0) {                                        // wave-uniform
+                    const uint32_t cw = surv_count(aw, ~(uint64_t)0);
+                    if (cw != 0) {
+                        unsigned long long wbase = 0;
+                        if (lane == 0) {
+                            wbase = atomicAdd(&totals->n_small, (unsigned long long)cw);
+                            atomicAdd(&totals->n_wide_pairs, (unsigned long long)cw);
+                            if (wbase + cw > small_cap) { atomicOr(&totals->overflow, 1ull); wbase = ~0ull; }
+                        }
+                        wbase = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(wbase >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)wbase);
+                        if (wbase != ~0ull) {
+                            unsigned long long at = wbase + surv_rank(aw, lane);
+#pragma unroll
+                            for (int b = 0; b < SURV_PER_LANE; ++b) {
+                                const uint32_t kw = surv_lane_bit(aw[b], lane);
+                                if (kw) { pa[at] = x; pb[at] = word(b) & 0x3fffffffu; }
+                                at += kw;
+                            }
+                        }
+                    }
+                }
+                fill = (uint32_t)__builtin_amdgcn_readfirstlane((int)fill);          // (wave-uniform, and the compiler should know it)
+                fill_n = (uint32_t)__builtin_amdgcn_readfirstlane((int)fill_n);
+                surv_batch(am, an, fill, fill_n, NN_LIST_CHUNK,
+                           [&](uint64_t lanes, uint32_t off_a, uint32_t off_n) {
+                               if (surv_lane_bit(lanes, lane) == 0) return;
+                               uint32_t at_a = off_a + surv_rank(am, lane), at_n = (uint32_t)NN_STAGE - 1u - (off_n + surv_rank(an, lane));
+#pragma unroll
+                               for (int b = 0; b < SURV_PER_LANE; ++b) {
+                                   const uint32_t ka = surv_lane_bit(am[b], lane), kn = surv_lane_bit(an[b], lane);
+                                   if (ka | kn) st[ka ? at_a : at_n] = word(b);
+                                   at_a += ka;
+                                   at_n -= kn;
+                               }
+                           },
+                           [&](bool narrow_class) { emit_chunk(narrow_class); });          // the buffer is full: its larger class leaves (>= half a chunk)
+            }
+        };
+        for (uint32_t c0 = 0; c0 < len; c0 += SURV_BATCH * U) {
+            uint32_t lbv[U];
+            NNMeta4 my[U];
+            load_batches(c0, lbv, my);
+            scan_batches(c0, lbv, my);
         }
     };
     scan_side(std::integral_constant<int, 0>());
@@ -217,6 +272,8 @@ __global__ __launch_bounds__(64 * NN_SURV_WAVES) void k_nn_survivors(DevStore S,
     // what is left of both classes goes to the pair arrays (the pair-per-lane kernel takes any threshold)
     const uint32_t rest = fill + fill_n;
     // what is left goes to the pair arrays: one allocation per workgroup
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { filtered += __shfl_xor(filtered, o, 64); kept += __shfl_xor(kept, o, 64); }          // (counted per lane in the scan)
     if (lane == 0) { s_small[wave] = rest; s_filtered[wave] = filtered; s_kept[wave] = kept; }
     __syncthreads();
     if (threadIdx.x == 0) {
