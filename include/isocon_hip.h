@@ -417,7 +417,7 @@ int isocon_hw_path_pairs(isocon_store *s, const uint32_t *q, const uint32_t *t, 
  * Device read tables of the hypothesis test: which reads support a candidate against its reference, and every read's error counts,
  * from the stored read alignments -- the per-read loops of get_support (modules/functions.py:149-201), get_read_errors (:204-216) and
  * read_errors_from_alignment (:495-522) as arrange_alignments_new_no_realign calls them per edge (modules/hypothesis_test_module.py:92-171).
- * Integers and bit sets only: the probabilities and the p-value stay on the host.
+ * Integers and bit sets, and with base qualities the reads' error probabilities (isocon_readtab_probability); the p-value stays on the host.
  *
  * A table set holds the alignments of the reads of many candidates.  Row r is the pair of gapped rows (candidate's, read's)
  * ref_rows / read_rows[row_ptr[r] .. row_ptr[r + 1]) (one row_ptr: both rows of an alignment are equally long), table k = rows
@@ -467,6 +467,28 @@ int isocon_hw_path_pairs(isocon_store *s, const uint32_t *q, const uint32_t *t, 
  *                                both > neither > beyond > index > quality.  A byte depends on its own (variant, row) only: dropping a
  *                                read at an earlier variant, and raising for a read that is still informative, is the caller's.
  *                                ISOCON_E_ARG: no qualities attached.
+ *   isocon_readtab_probability   the queries of isocon_readtab_quality (the very arrays, snippets for both kinds, the same checks) answered
+ *                                with one double per row: what the variant loop of get_read_ccs_probabilities_c / _t
+ *                                (modules/functions.py:240-433) multiplies up for that read, so the code bytes never leave the device.
+ *                                q_ratios[3 q ..] = the (substitution, insertion, deletion) shares of the errors of query q's edge,
+ *                                p_of_quality[0 .. 93] = the error probability of every quality value.  A row starts informative with
+ *                                p = 1.0 and takes the query's variants in order; at a variant with code byte
+ *                                  0xFF       it stops being informative: its answer is -1.0, later variants do nothing to it;
+ *                                  0xFE / 0xFD / 0xFC  (while informative) it raises: its answer is -2.0, later variants do nothing;
+ *                                  0 .. 93    p = p * p_error with p10 = p_of_quality[code] and p_error = p10 if u_v > 1, else
+ *                                             (p10 * substitution share) / 3.0 for 'S', (p10 * insertion share) / 4.0 for 'I',
+ *                                             p10 * deletion share for any other type (:305-320, :406-421)
+ *                                in IEEE binary64, each product and quotient rounded once, in exactly that association: equal to the
+ *                                host's doubles in every bit, subnormal and zero products included (whether 0 < p < 1 holds is the
+ *                                caller's to assert).  out_prob[prob_ptr[q] + j] = row j of query q's table; the caller sizes the range
+ *                                (prob_ptr[q + 1] - prob_ptr[q] >= rows, prob_ptr[0] = 0; spare slots come back 0.0); a query without
+ *                                variants answers 1.0 for every row.  out_status[q] = 0 if no row of the query raised, else
+ *                                ((v + 1) << 8) | code byte of what the per-read statements meet first: the smallest variant index v
+ *                                (0-based in the query) at which an informative row raises, and among the rows at that variant both
+ *                                (0xFE, an assertion) before beyond (0xFD, an exit) before index (0xFC, IndexError).  The answers of
+ *                                a query with a non-zero status are not the reference's: it raises there.  ISOCON_E_ARG: no qualities
+ *                                attached; q_ratios, p_of_quality, prob_ptr or out_status NULL; more than 2^24 - 2 variants in a query;
+ *                                and whatever isocon_readtab_quality refuses.
  *   isocon_readtab_device_bytes  device memory the handle holds (the qualities' buffers included).
  */
 typedef struct isocon_readtab isocon_readtab;
@@ -479,6 +501,10 @@ int isocon_readtab_set_qualities(isocon_readtab *h, const uint8_t *qual, const u
 int isocon_readtab_quality(isocon_readtab *h, uint32_t n_queries, const uint32_t *q_table, const uint8_t *q_kind, const uint64_t *var_ptr,
                            const int32_t *var_pos, const int32_t *var_u, const uint8_t *var_type, const uint64_t *snip_ptr, const uint8_t *snip_bytes,
                            const uint64_t *code_ptr, uint8_t *out_codes, float *kernel_ms);
+int isocon_readtab_probability(isocon_readtab *h, uint32_t n_queries, const uint32_t *q_table, const uint8_t *q_kind, const uint64_t *var_ptr,
+                               const int32_t *var_pos, const int32_t *var_u, const uint8_t *var_type, const uint64_t *snip_ptr, const uint8_t *snip_bytes,
+                               const double *q_ratios /* 3 per query: substitution, insertion, deletion */, const double *p_of_quality /* 94 */,
+                               const uint64_t *prob_ptr, double *out_prob, uint32_t *out_status, float *kernel_ms);
 void isocon_readtab_destroy(isocon_readtab *h);
 uint64_t isocon_readtab_device_bytes(const isocon_readtab *h);
 

@@ -25,6 +25,7 @@ u32p = ctypes.POINTER(ctypes.c_uint32)
 i32p = ctypes.POINTER(ctypes.c_int32)
 u64p = ctypes.POINTER(ctypes.c_uint64)
 f32p = ctypes.POINTER(ctypes.c_float)
+f64p = ctypes.POINTER(ctypes.c_double)
 
 
 class NNStats(ctypes.Structure):
@@ -104,6 +105,7 @@ SYMBOLS = {
     "isocon_readtab_support": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, u32p, u8p, u64p, i32p, i32p, u8p, u64p, u8p, u64p, u64p, u32p, f32p]),
     "isocon_readtab_set_qualities": (ctypes.c_int, [ctypes.c_void_p, u8p, u64p, u32p, f32p]),
     "isocon_readtab_quality": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, u32p, u8p, u64p, i32p, i32p, u8p, u64p, u8p, u64p, u8p, f32p]),
+    "isocon_readtab_probability": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, u32p, u8p, u64p, i32p, i32p, u8p, u64p, u8p, f64p, f64p, u64p, f64p, u32p, f32p]),
     "isocon_readtab_destroy": (None, [ctypes.c_void_p]),
     "isocon_readtab_device_bytes": (ctypes.c_uint64, [ctypes.c_void_p]),
     "isocon_edge_variants": (ctypes.c_int, [u8p, u64p, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p, u32p, u64p, u64p, u8p, u32p, u8p, i32p, u64p, u8p, u8p,

@@ -13,6 +13,10 @@
 //   k_rt_quality  one wavefront per query as in k_rt_support; per variant every lane writes one byte, rt_quality_code of its row: the
 //                 quality at the variant's place in the read's record or the reason there is none.  The 64 bytes of a wavefront
 //                 and variant are one contiguous run.
+//   k_rt_probability  the same walk, but the code bytes stay in the lane: every row keeps (alive, p) in registers over the variant loop
+//                 and multiplies its error probability up as the host's _ccs_probabilities_from_codes does, bit for bit
+//                 (rt_probability_step); one double per row at the end.  What the host would raise becomes the query's status word: the
+//                 minimum of (variant << 2 | rank) over the lanes' rows, by six xor-shuffles after the row loop.
 // No LDS, no scratch; lane 0 writes a wavefront's words.
 #pragma once
 #include "common.hpp"
@@ -172,6 +176,41 @@ __global__ __launch_bounds__(256) void k_rt_quality(RtTables T, RtQualities U, R
             out_codes[c0 + (v - v0) * nr + j] = rt_quality_code(R, Q.var_pos[v], Q.var_u[v], Q.var_type[v], kind, Q.snip_bytes + Q.snip_ptr[v],
                                                                 Q.snip_ptr[v + 1] - Q.snip_ptr[v], U.qual + q0, rec_len, rec_start);
     }
+}
+
+// out_prob[out_ptr[q] + j]: row j of the query's table -- its probability, -1.0 (not informative) or -2.0 (it raised); out_status[q]:
+// rt_prob_status of the smallest event key of the query's rows.  q_ratios: 3 doubles per query, p_of_quality: 94 doubles.
+__global__ __launch_bounds__(256) void k_rt_probability(RtTables T, RtQualities U, RtQueries Q, const double *__restrict__ q_ratios,
+                                                         const double *__restrict__ p_of_quality, double *__restrict__ out_prob, uint32_t *__restrict__ out_status)
+{
+    const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= Q.n) return;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t k = Q.q_table[q];
+    const uint32_t r0 = T.first_row[k], nr = T.first_row[k + 1] - r0;
+    const uint64_t v0 = Q.var_ptr[q], v1 = Q.var_ptr[q + 1], c0 = Q.out_ptr[q];
+    const int kind = Q.q_kind[q];
+    const double *ratios = q_ratios + (size_t)q * 3;
+    uint32_t first = RT_P_NO_EVENT;          // over this lane's rows of all 64-row passes
+    for (uint32_t j = lane; j < nr; j += 64) {
+        const uint64_t r = (uint64_t)r0 + j;
+        const uint64_t off = T.row_ptr[r], blk0 = T.blk_ptr[r], q0 = U.qual_ptr[r];
+        const RtRow R{T.nob + blk0, T.diff + blk0, T.pre + blk0, T.read + off, (uint32_t)(T.blk_ptr[r + 1] - blk0), (int64_t)(T.row_ptr[r + 1] - off), U.rgap + blk0,
+                      U.rpre + blk0};
+        const int64_t rec_len = (int64_t)(U.qual_ptr[r + 1] - q0), rec_start = U.rec_start[r];
+        RtProb s = rt_prob_init();
+        for (uint64_t v = v0; v < v1; ++v) {
+            const uint32_t key = rt_probability_step(s, (uint32_t)(v - v0), ratios, p_of_quality, R, Q.var_pos[v], Q.var_u[v], Q.var_type[v], kind,
+                                                     Q.snip_bytes + Q.snip_ptr[v], Q.snip_ptr[v + 1] - Q.snip_ptr[v], U.qual + q0, rec_len, rec_start);
+            first = key < first ? key : first;
+        }
+        out_prob[c0 + j] = s.p;
+    }
+    for (int w = 32; w >= 1; w >>= 1) {          // the wavefront's lanes are together again here: the minimum over all 64
+        const uint32_t other = (uint32_t)__shfl_xor((int)first, w);
+        first = other < first ? other : first;
+    }
+    if (lane == 0) out_status[q] = rt_prob_status(first);
 }
 
 }  // namespace isocon

@@ -208,4 +208,55 @@ ISO_HD uint8_t rt_quality_code(const RtRow &R, uint32_t i, int32_t u_v, uint8_t 
     return qual[coord];
 }
 
+// ---- the probabilities themselves: one read's share of one iteration of the variant loop of functions._ccs_probabilities ----
+
+// A row's running state over the variants of a query.  p: the product so far while alive; -1.0 once a variant found the read not
+// informative, -2.0 once it raised (alive is false from then on and later variants do nothing).
+struct RtProb {
+    double p;
+    bool alive;
+};
+ISO_HD RtProb rt_prob_init() { return RtProb{1.0, true}; }
+
+// what a step reports: nothing, or (variant index << 2 | rank) -- the smaller key is what the per-read statements meet first: variants
+// in order, and within a variant the assertion on BOTH (rank 0) before the exit on BEYOND (1) before the IndexError (2)
+constexpr uint32_t RT_P_NO_EVENT = 0xFFFFFFFFu;
+constexpr uint32_t RT_P_MAX_VARIANTS = (1u << 24) - 2;          // (variant index + 1) << 8 fits a status word
+
+// the status word of a query from the smallest key of its rows: 0 = no event, else (variant index + 1) << 8 | the code byte
+ISO_HD uint32_t rt_prob_status(uint32_t key) { return key == RT_P_NO_EVENT ? 0u : ((((key >> 2) + 1u) << 8) | (uint32_t)(RT_Q_BOTH - (key & 3u))); }
+
+// The step on a code byte.  ratios: substitution, insertion, deletion share of the edge's errors; p_of_quality: 94 error probabilities.
+// binary64 multiplications and divisions in the association of the reference, never contracted, no reciprocal: the product is the
+// reference's to the last bit, subnormal results included.
+ISO_HD uint32_t rt_probability_apply(RtProb &s, uint8_t code, uint32_t v_index, int32_t u_v, uint8_t v_type, const double *ratios, const double *p_of_quality)
+{
+#pragma clang fp contract(off)
+    if (!s.alive) return RT_P_NO_EVENT;
+    if (code == RT_Q_NEITHER) {
+        s = RtProb{-1.0, false};
+        return RT_P_NO_EVENT;
+    }
+    if (code > 93) {          // BOTH, BEYOND or INDEX on a read that is still informative
+        s = RtProb{-2.0, false};
+        return (v_index << 2) | (uint32_t)(RT_Q_BOTH - code);
+    }
+    const double p10 = p_of_quality[code];
+    double p_error;
+    if (u_v > 1) p_error = p10;
+    else if (v_type == 'S') p_error = (p10 * ratios[0]) / 3.0;
+    else if (v_type == 'I') p_error = (p10 * ratios[1]) / 4.0;
+    else p_error = p10 * ratios[2];
+    s.p = s.p * p_error;
+    return RT_P_NO_EVENT;
+}
+
+// One iteration for one read: rt_quality_code (same arguments), then the step above; v_index: the variant's place in its query.
+ISO_HD uint32_t rt_probability_step(RtProb &s, uint32_t v_index, const double *ratios, const double *p_of_quality, const RtRow &R, uint32_t i, int32_t u_v, uint8_t v_type,
+                                    int kind, const uint8_t *snippet, uint64_t snippet_len, const uint8_t *qual, int64_t rec_len, int64_t rec_start)
+{
+    if (!s.alive) return RT_P_NO_EVENT;          // (nothing is looked up for a read that has left)
+    return rt_probability_apply(s, rt_quality_code(R, i, u_v, v_type, kind, snippet, snippet_len, qual, rec_len, rec_start), v_index, u_v, v_type, ratios, p_of_quality);
+}
+
 }  // namespace isocon

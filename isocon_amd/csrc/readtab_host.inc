@@ -1,5 +1,5 @@
 // readtab_host.inc -- host side of the device read tables of the statistical test (included by isocon_hip.hip): isocon_readtab_create /
-// _support / _set_qualities / _quality / _destroy / _device_bytes.  The tables live in the handle; the candidates' rows (needed by the build only), the queries and
+// _support / _set_qualities / _quality / _probability / _destroy / _device_bytes.  The tables live in the handle; the candidates' rows (needed by the build only), the queries and
 // the answers pass through slots of the process' scratch pool.
 
 struct isocon_readtab {
@@ -143,13 +143,20 @@ extern "C" int isocon_readtab_create(const uint8_t *ref_rows, const uint8_t *rea
 
 namespace {
 
-// The queries of isocon_readtab_support / _quality (`what`: the entry's name) checked against the handle and uploaded as one image into
-// d_in.  out_ptr: where query q's answer starts; it must hold ceil(rows / 64) words, or with `codes` variants x rows bytes.  Snippets are
-// needed by the queries of kind 1, with `codes` by all.  Coordinates in [-ref_len, 0) are wrapped as a Python index is.
+// What a query is answered with, and so how many slots its output range must hold.
+enum RtAnswer { RT_ANSWER_BITS,          // ceil(rows / 64) words
+                RT_ANSWER_CODES,         // variants x rows bytes
+                RT_ANSWER_PROBS };       // rows doubles
+
+// The queries of isocon_readtab_support / _quality / _probability (`what`: the entry's name) checked against the handle and uploaded as
+// one image into d_in.  out_ptr: where query q's answer starts; it must hold what `answer` says.  Snippets are needed by the queries of
+// kind 1, by all unless the answer is bits.  Coordinates in [-ref_len, 0) are wrapped as a Python index is.  tail / n_tail: doubles that
+// travel at the end of the image (the probability entry's ratios and table), *d_tail: where they are on the device.
 int rt_stage_queries(isocon_readtab *h, const char *what, uint32_t n_queries, const uint32_t *q_table, const uint8_t *q_kind, const uint64_t *var_ptr,
                      const int32_t *var_pos, const int32_t *var_u, const uint8_t *var_type, const uint64_t *snip_ptr, const uint8_t *snip_bytes, const uint64_t *out_ptr,
-                     bool codes, DevBuf &d_in, RtQueries &Q)
+                     RtAnswer answer, DevBuf &d_in, RtQueries &Q, const double *tail = nullptr, size_t n_tail = 0, const double **d_tail = nullptr)
 {
+    const bool codes = answer != RT_ANSWER_BITS;
     const std::string name = what;
     if (!q_table || !q_kind || !var_ptr || !out_ptr) return ISOCON_E_ARG;
     const uint64_t n_var = var_ptr[n_queries], n_out = out_ptr[n_queries];
@@ -163,7 +170,8 @@ int rt_stage_queries(isocon_readtab *h, const char *what, uint32_t n_queries, co
             return ISOCON_E_ARG;
         }
         const uint32_t k = q_table[q], nr = h->first_row[k + 1] - h->first_row[k];
-        const uint64_t need = codes ? (var_ptr[q + 1] - var_ptr[q]) * nr : ((uint64_t)nr + 63) / 64;
+        const uint64_t need = answer == RT_ANSWER_CODES ? (var_ptr[q + 1] - var_ptr[q]) * nr : answer == RT_ANSWER_PROBS ? (uint64_t)nr : ((uint64_t)nr + 63) / 64;
+        if (answer == RT_ANSWER_PROBS && var_ptr[q + 1] - var_ptr[q] > RT_P_MAX_VARIANTS) { g_last_error = name + ": too many variants in query " + std::to_string(q); return ISOCON_E_ARG; }
         if (out_ptr[q + 1] - out_ptr[q] < need) { g_last_error = name + ": the output range of query " + std::to_string(q) + " is too small"; return ISOCON_E_ARG; }
         const int64_t ref_len = h->ref_len[k];
         for (uint64_t v = var_ptr[q]; v < var_ptr[q + 1]; ++v) {
@@ -195,13 +203,14 @@ int rt_stage_queries(isocon_readtab *h, const char *what, uint32_t n_queries, co
     const size_t o_var_ptr = rt_pack(img, var_ptr, (size_t)n_queries + 1), o_snip_ptr = rt_pack(img, snip_rel.data(), snip_rel.size()),
                  o_out_ptr = rt_pack(img, out_ptr, (size_t)n_queries + 1), o_table = rt_pack(img, q_table, n_queries), o_pos = rt_pack(img, pos.data(), pos.size()),
                  o_u = rt_pack(img, var_u, (size_t)n_var), o_kind = rt_pack(img, q_kind, n_queries), o_type = rt_pack(img, var_type, (size_t)n_var),
-                 o_snip = rt_pack(img, snip_total ? snip_bytes + snip_base : nullptr, (size_t)snip_total);
+                 o_snip = rt_pack(img, snip_total ? snip_bytes + snip_base : nullptr, (size_t)snip_total), o_tail = rt_pack(img, tail, n_tail);
     int rc;
     if ((rc = d_in.alloc(img.size()))) return rc;
     ISO_HIP_CHECK(copy_h2d(d_in.p, img.data(), img.size()));
     const uint8_t *in = d_in.as<uint8_t>();
     Q = RtQueries{(const uint32_t *)(in + o_table), in + o_kind, (const uint64_t *)(in + o_var_ptr), (const uint32_t *)(in + o_pos), (const int32_t *)(in + o_u), in + o_type,
                   (const uint64_t *)(in + o_snip_ptr), in + o_snip, (const uint64_t *)(in + o_out_ptr), n_queries};
+    if (d_tail) *d_tail = (const double *)(in + o_tail);
     return ISOCON_OK;
 }
 
@@ -218,7 +227,7 @@ extern "C" int isocon_readtab_support(isocon_readtab *h, uint32_t n_queries, con
     DevBuf d_in(&g_scratch, SLOT_RT_IN), d_out(&g_scratch, SLOT_RT_OUT);
     RtQueries Q;
     int rc;
-    if ((rc = rt_stage_queries(h, "isocon_readtab_support", n_queries, q_table, q_kind, var_ptr, var_pos, var_u, var_type, snip_ptr, snip_bytes, bits_ptr, false, d_in, Q)))
+    if ((rc = rt_stage_queries(h, "isocon_readtab_support", n_queries, q_table, q_kind, var_ptr, var_pos, var_u, var_type, snip_ptr, snip_bytes, bits_ptr, RT_ANSWER_BITS, d_in, Q)))
         return rc;
     const uint64_t n_words = bits_ptr[n_queries];
     const size_t out_bytes = (size_t)n_words * 8 + (size_t)n_queries * 4;
@@ -288,7 +297,7 @@ extern "C" int isocon_readtab_quality(isocon_readtab *h, uint32_t n_queries, con
     DevBuf d_in(&g_scratch, SLOT_RT_IN), d_out(&g_scratch, SLOT_RT_OUT);
     RtQueries Q;
     int rc;
-    if ((rc = rt_stage_queries(h, "isocon_readtab_quality", n_queries, q_table, q_kind, var_ptr, var_pos, var_u, var_type, snip_ptr, snip_bytes, code_ptr, true, d_in, Q)))
+    if ((rc = rt_stage_queries(h, "isocon_readtab_quality", n_queries, q_table, q_kind, var_ptr, var_pos, var_u, var_type, snip_ptr, snip_bytes, code_ptr, RT_ANSWER_CODES, d_in, Q)))
         return rc;
     const uint64_t n_codes = code_ptr[n_queries];
     if (!n_codes) return ISOCON_OK;
@@ -303,5 +312,43 @@ extern "C" int isocon_readtab_quality(isocon_readtab *h, uint32_t n_queries, con
     tm.stop();
     if (kernel_ms) *kernel_ms = tm.total;
     ISO_HIP_CHECK(copy_d2h(out_codes, d_out.p, (size_t)n_codes));
+    return ISOCON_OK;
+}
+
+extern "C" int isocon_readtab_probability(isocon_readtab *h, uint32_t n_queries, const uint32_t *q_table, const uint8_t *q_kind, const uint64_t *var_ptr,
+                                          const int32_t *var_pos, const int32_t *var_u, const uint8_t *var_type, const uint64_t *snip_ptr, const uint8_t *snip_bytes,
+                                          const double *q_ratios, const double *p_of_quality, const uint64_t *prob_ptr, double *out_prob, uint32_t *out_status,
+                                          float *kernel_ms)
+{
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (!h) return ISOCON_E_ARG;
+    if (!h->has_qualities) { g_last_error = "isocon_readtab_probability: the table set has no qualities (isocon_readtab_set_qualities)"; return ISOCON_E_ARG; }
+    if (!n_queries) return ISOCON_OK;
+    if (!q_ratios || !p_of_quality || !prob_ptr || !out_status || (prob_ptr[n_queries] && !out_prob)) return ISOCON_E_ARG;
+    DevBuf d_in(&g_scratch, SLOT_RT_IN), d_out(&g_scratch, SLOT_RT_OUT);
+    RtQueries Q;
+    std::vector<double> tail((size_t)n_queries * 3 + 94);          // the queries' ratios, then the table
+    memcpy(tail.data(), q_ratios, (size_t)n_queries * 3 * sizeof(double));
+    memcpy(tail.data() + (size_t)n_queries * 3, p_of_quality, 94 * sizeof(double));
+    const double *d_tail = nullptr;
+    int rc;
+    if ((rc = rt_stage_queries(h, "isocon_readtab_probability", n_queries, q_table, q_kind, var_ptr, var_pos, var_u, var_type, snip_ptr, snip_bytes, prob_ptr, RT_ANSWER_PROBS,
+                               d_in, Q, tail.data(), tail.size(), &d_tail)))
+        return rc;
+    const uint64_t n_prob = prob_ptr[n_queries];
+    const size_t out_bytes = (size_t)n_prob * 8 + (size_t)n_queries * 4;
+    if ((rc = d_out.alloc(out_bytes))) return rc;
+    if (n_prob) ISO_HIP_CHECK(hipMemset(d_out.p, 0, (size_t)n_prob * 8));          // (slots beyond a table's rows)
+    RtTables T{h->d_row_ptr, h->d_blk_ptr, h->d_nob, h->d_diff, h->d_pre, h->d_read, h->d_first};
+    RtQualities U{h->d_rgap, h->d_rpre, h->d_qual, h->d_qual_ptr, h->d_rec_start};
+    uint32_t *d_status = (uint32_t *)(d_out.as<uint8_t>() + (size_t)n_prob * 8);
+    EventTimer tm;
+    tm.start();
+    hipLaunchKernelGGL(k_rt_probability, dim3((n_queries + 3) / 4), dim3(256), 0, 0, T, U, Q, d_tail, d_tail + (size_t)n_queries * 3, d_out.as<double>(), d_status);
+    ISO_HIP_CHECK(hipGetLastError());
+    tm.stop();
+    if (kernel_ms) *kernel_ms = tm.total;
+    if (n_prob) ISO_HIP_CHECK(copy_d2h(out_prob, d_out.p, (size_t)n_prob * 8));
+    ISO_HIP_CHECK(copy_d2h(out_status, d_status, (size_t)n_queries * 4));
     return ISOCON_OK;
 }

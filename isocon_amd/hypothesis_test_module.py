@@ -12,7 +12,8 @@ The reference aligns the two orders of every edge one call at a time (or one Poo
 round go to the GPU as one batch of isocon_sg_strings_batch (2 x edges alignments), everything after that is string
 bookkeeping on the host as in the reference.  With base qualities (a `ccs_dict`: FASTQ input) the error probabilities
 come from the qualities (functions.get_read_ccs_probabilities_c / _t): which quality a read contributes at a variant is
-looked up on the same read tables (isocon_readtab_quality on the device tables), the floats stay on the host."""
+looked up on the same read tables, and on the device tables the lanes multiply the reads' error probabilities up as well
+(isocon_readtab_probability: the host's doubles bit for bit); the logarithms, the sums and the bound stay on the host."""
 from __future__ import annotations
 
 import ctypes
@@ -160,6 +161,29 @@ def _quality_codes_on_table(tab, i, v_type, u_v, alive, other_snippet, ccs_dict,
     return np.where(shows_own & shows_other, _Q_BOTH, code).astype(np.uint8)
 
 
+_P_OF_QUALITY = {}     # max_phred_q_trusted -> the 94 error probabilities (read-only array)
+
+
+def _p_of_quality(max_phred_q_trusted):
+    """the error probability of every quality value 0 .. 93 mapped onto [3, max_phred_q_trusted] (functions._ccs_probabilities:
+    q_qual_mapped, 10 ** (-q_qual_mapped / 10.0)), made once per max_phred_q_trusted: the host route and the device route read the same doubles"""
+    base = _P_OF_QUALITY.get(max_phred_q_trusted)
+    if base is None:
+        base = np.asarray([10 ** (-((q - 3) * (max_phred_q_trusted - 3.0) / (90.0) + 3) / 10.0) for q in range(94)], dtype=np.float64)
+        base.setflags(write=False)
+        _P_OF_QUALITY[max_phred_q_trusted] = base
+    return base
+
+
+def _error_ratios(tab_c, tab_t):
+    """(substitution, insertion, deletion) shares of the errors of the reads of an edge (functions.get_read_ccs_probabilities_c / _t)"""
+    subs = float(max(1.0, int(tab_t.sub.sum() + tab_c.sub.sum())))
+    ins = float(max(1.0, int(tab_t.ins.sum() + tab_c.ins.sum())))
+    del_ = float(max(1.0, int(tab_t.dele.sum() + tab_c.dele.sum())))
+    tot_errors = subs + ins + del_
+    return (subs / tot_errors, ins / tot_errors, del_ / tot_errors)
+
+
 def _ccs_probabilities_from_codes(n, variant_coords, code_of, ratios, max_phred_q_trusted):
     """functions._ccs_probabilities for the n reads of a table at once: (informative mask, probability per read).  code_of(v, i, v_type,
     u_v, alive) gives the reads' code bytes at the v-th variant: _quality_codes_on_table on the host tables, a row of
@@ -170,7 +194,7 @@ def _ccs_probabilities_from_codes(n, variant_coords, code_of, ratios, max_phred_
     prob = np.ones(n, dtype=np.float64)
     if n == 0:
         return alive, prob
-    base = np.asarray([10 ** (-((q - 3) * (max_phred_q_trusted - 3.0) / (90.0) + 3) / 10.0) for q in range(94)], dtype=np.float64)
+    base = _p_of_quality(max_phred_q_trusted)
     for v, (i, (v_type, _, u_v)) in enumerate(variant_coords.items()):
         code = code_of(v, i, v_type, u_v, alive)
         assert not (alive & (code == _Q_BOTH)).any()
@@ -193,8 +217,13 @@ def _ccs_probabilities_from_codes(n, variant_coords, code_of, ratios, max_phred_
     return alive, prob
 
 
-def _ccs_probabilities_on_table(tab, variant_coords, other_snippets, ccs_dict, ratios, max_phred_q_trusted, shifted_type, coord_when_other, codes=None):
-    """_ccs_probabilities_from_codes for a table: a device table brings its codes (variants x reads), a host table computes them"""
+def _ccs_probabilities_on_table(tab, variant_coords, other_snippets, ccs_dict, ratios, max_phred_q_trusted, shifted_type, coord_when_other, codes=None, probs=None):
+    """_ccs_probabilities_from_codes for a table: a device table brings its codes (variants x reads) -- or the finished products (probs:
+    one double per read, negative = not informative; isocon_readtab_probability) --, a host table computes them"""
+    if probs is not None:
+        alive = probs >= 0
+        assert ((probs[alive] > 0.0) & (probs[alive] < 1.0)).all()
+        return alive, probs
     if codes is not None:
         return _ccs_probabilities_from_codes(tab.n, variant_coords, lambda v, i, v_type, u_v, alive: codes[v], ratios, max_phred_q_trusted)
     return _ccs_probabilities_from_codes(tab.n, variant_coords, lambda v, i, v_type, u_v, alive: _quality_codes_on_table(
@@ -340,8 +369,12 @@ def _tables_for(wanted, cache=None, build=None):
 
 # ---- the read tables on the device (isocon_readtab_*: csrc/readtab.hpp) ----
 # The integer work of a test -- the column of a candidate position in every read's alignment, the window comparisons, the error
-# counts -- for all edges of a round in one call per table set; the probabilities and the bound stay on the host (_test_on_supporters).
-DEVICE_STATS = {"create_calls": 0, "rows_uploaded": 0, "support_calls": 0, "queries": 0, "quality_attach_calls": 0, "quality_calls": 0, "kernel_ms": 0.0}
+# counts -- for all edges of a round in one call per table set, and with base qualities every read's error probability over the variants
+# of its edge; the logarithms, the sums and the bound stay on the host (_test_on_supporters).
+# quality_calls: one per table set and round whose quality queries were answered (by either entry; a codes call for an edge that raises
+# counts too), probability_calls: the calls of isocon_readtab_probability
+DEVICE_STATS = {"create_calls": 0, "rows_uploaded": 0, "support_calls": 0, "queries": 0, "quality_attach_calls": 0, "quality_calls": 0, "probability_calls": 0,
+                "kernel_ms": 0.0}
 _HAS_DEVICE = None
 
 
@@ -358,6 +391,12 @@ def device_tables_enabled():
     if _HAS_DEVICE is None:
         _HAS_DEVICE = _lib.load().isocon_device_count() > 0
     return _HAS_DEVICE
+
+
+def probabilities_on_device_enabled():
+    """with base qualities the reads' probabilities come from the device (isocon_readtab_probability) and not from its code bytes:
+    the device tables are on and ISOCON_DEBUG_VARIANT=stat_host_prob is not set"""
+    return device_tables_enabled() and not _variant_listed("stat_host_prob")
 
 
 def device_table_bytes():
@@ -544,14 +583,53 @@ def _device_quality(handle, queries):
     return [codes[int(code_ptr[q]):int(code_ptr[q + 1])].reshape(len(coords), n_rows) for q, (_, _, coords, _, n_rows) in enumerate(queries)]
 
 
+PROBABILITY_CALL_BYTES = 256 << 20          # a set's queries are split over several calls only if their doubles exceed this
+
+
+def _device_probability(handle, queries, ratios, max_phred_q_trusted):
+    """isocon_readtab_probability for the queries of _pack_queries (snippets for both kinds; ratios: per query the edge's _error_ratios):
+    per query (float64 per row of its table -- the read's probability, -1.0 where it is not informative --, status); a status other
+    than 0 says what the codes route raises for this query: (variant index + 1) << 8 | code byte.  One call unless the answers exceed
+    PROBABILITY_CALL_BYTES."""
+    out, lo = [], 0
+    while lo < len(queries):
+        hi, rows = lo + 1, queries[lo][4]
+        while hi < len(queries) and (rows + queries[hi][4]) * 8 <= PROBABILITY_CALL_BYTES:
+            rows += queries[hi][4]
+            hi += 1
+        out.extend(_device_probability_call(handle, queries[lo:hi], ratios[lo:hi], max_phred_q_trusted))
+        lo = hi
+    return out
+
+
+def _device_probability_call(handle, queries, ratios, max_phred_q_trusted):
+    q_table, q_kind, var_ptr, var_pos, var_u, var_type, snip_ptr, snip_bytes, _ = _pack_queries(queries)
+    prob_ptr = np.zeros(len(queries) + 1, dtype=np.uint64)
+    np.cumsum(np.asarray([n_rows for _, _, _, _, n_rows in queries], dtype=np.uint64), out=prob_ptr[1:])
+    probs = np.zeros(max(int(prob_ptr[-1]), 1), dtype=np.float64)
+    status = np.zeros(len(queries), dtype=np.uint32)
+    q_ratios = np.ascontiguousarray(ratios, dtype=np.float64).reshape(len(queries), 3)
+    base = _p_of_quality(max_phred_q_trusted)
+    ms = ctypes.c_float(0.0)
+    _lib.check(_lib.lib().isocon_readtab_probability(handle, len(queries), _ptr(q_table, _lib.u32p), _ptr(q_kind, _lib.u8p), _ptr(var_ptr, _lib.u64p),
+                                                     _ptr(var_pos, _lib.i32p), _ptr(var_u, _lib.i32p), _ptr(var_type, _lib.u8p), _ptr(snip_ptr, _lib.u64p),
+                                                     _ptr(snip_bytes, _lib.u8p), _ptr(q_ratios, _lib.f64p), _ptr(base, _lib.f64p), _ptr(prob_ptr, _lib.u64p),
+                                                     _ptr(probs, _lib.f64p), _ptr(status, _lib.u32p), ctypes.byref(ms)), "isocon_readtab_probability")
+    DEVICE_STATS["probability_calls"] += 1
+    DEVICE_STATS["kernel_ms"] += ms.value
+    ptr, status = prob_ptr.tolist(), status.tolist()
+    return [(probs[ptr[q]:ptr[q + 1]], status[q]) for q in range(len(queries))]
+
+
 def _in_range(coords, ref_len):
     return all(-ref_len <= i < ref_len for i in coords)
 
 
 def _tests_on_device(live, of_edge, C, read_partition, ccs_dict=None, max_phred_q_trusted=None, variants_of=None):
     """{edge: (variant_coords_t, p_value, supporting reads, reads used)} for the edges of a round: supporters and error counts from the
-    device tables, one support call per table set; with base qualities (ccs_dict) also every read's quality code at every variant, one
-    quality call per table set.  An edge with a variant coordinate that the per-read statement cannot index stays on the host tables,
+    device tables, one support call per table set; with base qualities (ccs_dict) also every read's probability (or, under
+    ISOCON_DEBUG_VARIANT=stat_host_prob, its quality code at every variant for the host to multiply up), one call per table set.  An edge
+    for which the device reports that something is to be raised goes through the codes, where it is raised.  An edge with a variant coordinate that the per-read statement cannot index stays on the host tables,
     where it raises as it always did; so does an edge of a table set whose qualities cannot be attached.  variants_of: {edge: the tuple
     of _edge_variants} where the caller has them (_edge_variants_on_device); of_edge[e], the two gapped alignments, is then looked at
     only for the edges that stay on the host tables (_LazyAlignments)."""
@@ -569,28 +647,44 @@ def _tests_on_device(live, of_edge, C, read_partition, ccs_dict=None, max_phred_
             if not all(tables[id(read_partition[acc])].set.attach_qualities(ccs_dict) for acc in e):
                 del prepared[e]
                 on_host.append(e)
-    by_set = {}          # id(set) -> (set, its support queries, where each answer goes, its quality queries, where each answer goes)
+    on_device_prob = bool(ccs_dict) and probabilities_on_device_enabled()
+    by_set = {}          # id(set) -> (set, its support queries, where each answer goes, its quality queries, where each answer goes, their ratios)
     for e, ev in prepared.items():
         tab_c, tab_t = tables[id(read_partition[e[0]])], tables[id(read_partition[e[1]])]
+        ratios = _error_ratios(tab_c, tab_t) if on_device_prob and len(ev[0]) > 0 else None
         for side, tab, kind, coords, snippets, others in ((0, tab_c, 0, ev[2], None, ev[4]), (1, tab_t, 1, ev[1], ev[3], ev[3])):
-            group = by_set.setdefault(id(tab.set), (tab.set, [], [], [], []))
+            group = by_set.setdefault(id(tab.set), (tab.set, [], [], [], [], []))
             group[1].append((tab.k, kind, coords, snippets, tab.n))
             group[2].append((e, side))
             if ccs_dict and len(ev[0]) > 0:          # (no variants: the test looks at no quality)
                 group[3].append((tab.k, kind, coords, others, tab.n))
                 group[4].append((e, side))
-    supporters, codes = {}, {}
-    for dset, queries, where, quality_queries, quality_where in by_set.values():
+                group[5].append(ratios)
+    supporters, codes, probs, asked = {}, {}, {}, {}
+    for dset, queries, where, quality_queries, quality_where, quality_ratios in by_set.values():
         for key, sup in zip(where, _device_support(dset.handle, queries)):
             supporters[key] = sup
-        for key, code in zip(quality_where, _device_quality(dset.handle, quality_queries)):
-            codes[key] = code
+        if on_device_prob and quality_queries:
+            for key, query, answer in zip(quality_where, quality_queries, _device_probability(dset.handle, quality_queries, quality_ratios, max_phred_q_trusted)):
+                probs[key], asked[key] = answer, (dset.handle, query)
+            DEVICE_STATS["quality_calls"] += 1
+        else:
+            for key, code in zip(quality_where, _device_quality(dset.handle, quality_queries)):
+                codes[key] = code
     results = {}
     for e, ev in prepared.items():
         variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c = ev
+        probs_c, probs_t = probs.get((e, 0)), probs.get((e, 1))
+        if probs_c is not None and (probs_c[1] or probs_t[1]):
+            # something is to be raised on this edge: its code bytes, and the host's loop over them raises it (c's reads before t's)
+            for side in (0, 1):
+                handle, query = asked[(e, side)]
+                codes[(e, side)] = _device_quality(handle, [query])[0]
+            probs_c = probs_t = None
         results[e] = _test_on_supporters(C[e[1]], variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c,
                                          tables[id(read_partition[e[0]])], tables[id(read_partition[e[1]])], supporters[(e, 0)], supporters[(e, 1)],
-                                         ccs_dict, max_phred_q_trusted, codes.get((e, 0)), codes.get((e, 1)))
+                                         ccs_dict, max_phred_q_trusted, codes.get((e, 0)), codes.get((e, 1)),
+                                         None if probs_c is None else probs_c[0], None if probs_t is None else probs_t[0])
     if on_host:
         host = _tables_for([(C[acc], read_partition[acc]) for e in on_host for acc in e])
         for e in on_host:
@@ -758,23 +852,20 @@ def _test_on_tables(t_seq, c_seq, alignment_tc, alignment_ct, tab_c, tab_t, ccs_
 
 
 def _test_on_supporters(t_seq, variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c, tab_c, tab_t, sup_c, sup_t,
-                        ccs_dict=None, max_phred_q_trusted=None, codes_c=None, codes_t=None):
+                        ccs_dict=None, max_phred_q_trusted=None, codes_c=None, codes_t=None, probs_c=None, probs_t=None):
     """The test of an edge once the supporting reads are known (sup_c / sup_t: ascending row indices into the tables of c / t, host
-    or device tables alike): error probabilities per read and the bound.  With base qualities, device tables bring codes_c / codes_t
-    (isocon_readtab_quality: variants x reads); host tables compute theirs."""
+    or device tables alike): error probabilities per read and the bound.  With base qualities, device tables bring probs_c / probs_t
+    (isocon_readtab_probability: one double per read, negative = not informative) or codes_c / codes_t (isocon_readtab_quality:
+    variants x reads); host tables compute theirs."""
     n_support = len(sup_c) + len(sup_t)
     if len(variants) == 0:
         return variant_coords_t, 0.0, n_support, tab_c.n + tab_t.n
     if ccs_dict:
         # base qualities (functions.get_read_ccs_probabilities_c / _t): c's informative reads first, then t's
-        subs = float(max(1.0, int(tab_t.sub.sum() + tab_c.sub.sum())))
-        ins = float(max(1.0, int(tab_t.ins.sum() + tab_c.ins.sum())))
-        del_ = float(max(1.0, int(tab_t.dele.sum() + tab_c.dele.sum())))
-        tot_errors = subs + ins + del_
-        ratios = (subs / tot_errors, ins / tot_errors, del_ / tot_errors)
-        alive_c, prob_c = _ccs_probabilities_on_table(tab_c, variant_coords_c, alignment_t_to_c, ccs_dict, ratios, max_phred_q_trusted, "D", {"I": 0}, codes_c)
+        ratios = _error_ratios(tab_c, tab_t) if probs_c is None or probs_t is None else None          # (the device had them with its queries)
+        alive_c, prob_c = _ccs_probabilities_on_table(tab_c, variant_coords_c, alignment_t_to_c, ccs_dict, ratios, max_phred_q_trusted, "D", {"I": 0}, codes_c, probs_c)
         alive_t, prob_t = _ccs_probabilities_on_table(tab_t, variant_coords_t, alignment_c_to_t, ccs_dict, ratios, max_phred_q_trusted, "I", {"D": 0, "I": -2},
-                                                      codes_t)
+                                                      codes_t, probs_t)
         prob = np.concatenate([prob_c[alive_c], prob_t[alive_t]])
         if len(prob) == 0:
             assert n_support == 0
