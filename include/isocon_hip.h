@@ -535,6 +535,25 @@ int isocon_edge_variants(const uint8_t *seqs, const uint64_t *seq_ptr, uint32_t 
                          float *kernel_ms);
 
 /*
+ * Raghavan's bound of hypothesis_test_module.py:253-329 for n tests: from m_sum[i] = E[Y] and y_sum[i] = the summed weights of the
+ * supporting reads the reference evaluates, in 100-digit decimals, d = y / m - 1, k = m d and e^k / (1 + d)^(k + k / d) and returns float()
+ * of it; y == 0 gives 1.0 and d == 0 gives 0.5.  As 1 + d = y / m, k = y - m and k / d = m, that is f = exp((y - m) - y (ln y - ln m)).  A lane
+ * evaluates f in 320-bit fixed point with a bound on its own error, to which the deviation of the reference's decimals from f (below 10^-89
+ * relative inside the domain) is added, and rounds to a double only where the discarded bits are farther from the halfway pattern than 2^22
+ * times that bound (kernel: isocon_amd/csrc/pbound.hpp, derivation: DESIGN.md 4.7).
+ *   out_certified[i] = 1: out_bound[i] has the bits of float() of the reference's 100-digit result.
+ *   out_certified[i] = 0: out_bound[i] comes back 0.0 and the caller evaluates the test itself (the reference statement then returns or
+ *                         raises what it always did).
+ * Certified domain: m and y finite, normal, positive and below 2^31, y |ln(y / m)| and |y - m| below floor(9 10^5 ln 10) = 2072326 (beyond
+ * y |log10(y / m)| = |y - m| log10(e) = 9 10^5 the decimals overflow or lose digits), and the exponent of y at most 300 below that of m (y / m >
+ * 2^-301: the reference's 1 + d keeps 100 - log10(m / y) digits of y / m, and below y / m = 5 10^-101 it is 0 and the reference raises).  Special cases, decided on the doubles' bits for such an
+ * m: y == +0.0 -> 1.0, y == m -> 0.5, both certified.  NaN, infinities, negative numbers (-0.0 too), m == 0 and subnormal inputs are never certified.
+ * No store, no handle.  n = 0 is ISOCON_OK; a NULL array with n > 0, or n > 2^32, ISOCON_E_ARG; no device ISOCON_E_NODEVICE.  Only the first n
+ * entries of the two outputs are written.
+ */
+int isocon_raghavan_bound(const double *m_sum, const double *y_sum, uint64_t n, double *out_bound, uint8_t *out_certified, float *kernel_ms);
+
+/*
  * Greedy partition of the nearest-neighbour graph into consensus centres and their members, on integer ids: what
  * get_partitions_no_copy (modules/partitions.py:301-413, called by partition_strings :416-593 on nx.reverse(G_star)) and
  * partition_highest_reachable_with_edge_degrees (modules/end_invariant_functions.py:405-533; nbr_tiebreak = 0) compute on networkx

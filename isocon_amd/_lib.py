@@ -16,7 +16,9 @@ SRC_DIR = os.path.join(_HERE, "csrc")
 _SOURCES = sorted(f for f in os.listdir(SRC_DIR) if f.endswith((".hip", ".hpp", ".inc"))) if os.path.isdir(SRC_DIR) else []
 
 ISOCON_OK = 0
+ISOCON_E_ARG = -1
 ISOCON_E_CAPACITY = -4
+ISOCON_E_NODEVICE = -5
 NN_INF = 0x3FFFFFFF
 
 u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -110,6 +112,7 @@ SYMBOLS = {
     "isocon_readtab_device_bytes": (ctypes.c_uint64, [ctypes.c_void_p]),
     "isocon_edge_variants": (ctypes.c_int, [u8p, u64p, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p, u32p, u64p, u64p, u8p, u32p, u8p, i32p, u64p, u8p, u8p,
                                             ctypes.c_uint64, u64p, f32p]),
+    "isocon_raghavan_bound": (ctypes.c_int, [f64p, f64p, ctypes.c_uint64, f64p, u8p, f32p]),
 }
 
 _lib = None

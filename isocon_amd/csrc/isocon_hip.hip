@@ -33,6 +33,7 @@
 #include "nn2_depth.hpp"
 #include "readtab.hpp"
 #include "edgevar.hpp"
+#include "pbound.hpp"
 
 namespace isocon {
 thread_local std::string g_last_error;
@@ -135,6 +136,7 @@ enum {
     SLOT_PACK_ASCII, SLOT_PACK_OFF, SLOT_PACK_BAD, SLOT_PACK_HIST, SLOT_PACK_FLAGS, SLOT_EB_A, SLOT_EB_B, SLOT_EB_K, SLOT_EB_OUT, SLOT_EB_ROWS, SLOT_SCAN_TMP, SLOT_SCAN_SUMS,
     SLOT_RT_REF, SLOT_RT_IN, SLOT_RT_OUT,
     SLOT_EV_IN, SLOT_EV_OUT, SLOT_EV_SNIP,
+    SLOT_PB_IN, SLOT_PB_OUT,
     SLOT_NWP_Q, SLOT_NWP_T, SLOT_NWP_ED, SLOT_NWP_TOFF, SLOT_NWP_ROFF, SLOT_NWP_REV, SLOT_NWP_RUNS, SLOT_NWP_FOFF, SLOT_NWP_OPS, SLOT_NWP_START, SLOT_NWP_COLS,
     SLOT_COUNT
 };
@@ -1151,6 +1153,7 @@ extern "C" int isocon_block_bound_pairs(isocon_store *s, const uint32_t *owner, 
 #include "hw_path_host.inc"
 #include "readtab_host.inc"
 #include "edgevar_host.inc"
+#include "pbound_host.inc"
 
 extern "C" int isocon_partition_ids(uint32_t n, const int32_t *degree, uint64_t n_edges, const uint32_t *edge_a, const uint32_t *edge_b,
                                     const uint32_t *rank, int32_t nbr_tiebreak, uint32_t *out_centre, int64_t *out_weight,

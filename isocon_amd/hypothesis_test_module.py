@@ -13,7 +13,9 @@ round go to the GPU as one batch of isocon_sg_strings_batch (2 x edges alignment
 bookkeeping on the host as in the reference.  With base qualities (a `ccs_dict`: FASTQ input) the error probabilities
 come from the qualities (functions.get_read_ccs_probabilities_c / _t): which quality a read contributes at a variant is
 looked up on the same read tables, and on the device tables the lanes multiply the reads' error probabilities up as well
-(isocon_readtab_probability: the host's doubles bit for bit); the logarithms, the sums and the bound stay on the host."""
+(isocon_readtab_probability: the host's doubles bit for bit); the logarithms and the sums stay on the host.  The bound itself
+(_raghavan_from_sums: 100-digit decimals) is evaluated for all edges of a round by one isocon_raghavan_bound call, in wide fixed point
+with a certificate per test that its double is float() of the decimal result; a test without it goes through _raghavan_from_sums."""
 from __future__ import annotations
 
 import ctypes
@@ -370,7 +372,7 @@ def _tables_for(wanted, cache=None, build=None):
 # ---- the read tables on the device (isocon_readtab_*: csrc/readtab.hpp) ----
 # The integer work of a test -- the column of a candidate position in every read's alignment, the window comparisons, the error
 # counts -- for all edges of a round in one call per table set, and with base qualities every read's error probability over the variants
-# of its edge; the logarithms, the sums and the bound stay on the host (_test_on_supporters).
+# of its edge; the logarithms and the sums stay on the host (_test_on_supporters), the bounds of the round follow in one call (_device_bounds).
 # quality_calls: one per table set and round whose quality queries were answered (by either entry; a codes call for an edge that raises
 # counts too), probability_calls: the calls of isocon_readtab_probability
 DEVICE_STATS = {"create_calls": 0, "rows_uploaded": 0, "support_calls": 0, "queries": 0, "quality_attach_calls": 0, "quality_calls": 0, "probability_calls": 0,
@@ -632,7 +634,8 @@ def _tests_on_device(live, of_edge, C, read_partition, ccs_dict=None, max_phred_
     for which the device reports that something is to be raised goes through the codes, where it is raised.  An edge with a variant coordinate that the per-read statement cannot index stays on the host tables,
     where it raises as it always did; so does an edge of a table set whose qualities cannot be attached.  variants_of: {edge: the tuple
     of _edge_variants} where the caller has them (_edge_variants_on_device); of_edge[e], the two gapped alignments, is then looked at
-    only for the edges that stay on the host tables (_LazyAlignments)."""
+    only for the edges that stay on the host tables (_LazyAlignments).  The bounds of the edges on the device tables follow in one call after
+    their loop (_resolve_bounds) unless ISOCON_DEBUG_VARIANT=stat_host_bound is set."""
     prepared, on_host = {}, []
     for e in live:
         c_acc, t_acc = e
@@ -672,6 +675,23 @@ def _tests_on_device(live, of_edge, C, read_partition, ccs_dict=None, max_phred_
             for key, code in zip(quality_where, _device_quality(dset.handle, quality_queries)):
                 codes[key] = code
     results = {}
+    pending = [] if bounds_on_device_enabled() else None          # (m_sum, y_sum) of the tests whose bound is still to come
+    try:
+        _tests_of_prepared(results, pending, prepared, probs, asked, codes, supporters, tables, C, read_partition, ccs_dict, max_phred_q_trusted)
+    except (Exception, SystemExit):          # (what the tests themselves raise -- SystemExit is one of them --, not an interrupt)
+        _resolve_bounds(results, pending)          # the bound of an earlier edge that is to raise raises first, as it did
+        raise
+    _resolve_bounds(results, pending)
+    if on_host:
+        host = _tables_for([(C[acc], read_partition[acc]) for e in on_host for acc in e])
+        for e in on_host:
+            results[e] = _test_on_tables(C[e[1]], C[e[0]], of_edge[e][0], of_edge[e][1], host[id(read_partition[e[0]])], host[id(read_partition[e[1]])],
+                                         ccs_dict, max_phred_q_trusted)
+    return results
+
+
+def _tests_of_prepared(results, pending, prepared, probs, asked, codes, supporters, tables, C, read_partition, ccs_dict, max_phred_q_trusted):
+    """the loop of _tests_on_device over the edges on the device tables, in edge order; with `pending` the p-values are _PendingBound"""
     for e, ev in prepared.items():
         variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c = ev
         probs_c, probs_t = probs.get((e, 0)), probs.get((e, 1))
@@ -684,13 +704,72 @@ def _tests_on_device(live, of_edge, C, read_partition, ccs_dict=None, max_phred_
         results[e] = _test_on_supporters(C[e[1]], variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c,
                                          tables[id(read_partition[e[0]])], tables[id(read_partition[e[1]])], supporters[(e, 0)], supporters[(e, 1)],
                                          ccs_dict, max_phred_q_trusted, codes.get((e, 0)), codes.get((e, 1)),
-                                         None if probs_c is None else probs_c[0], None if probs_t is None else probs_t[0])
-    if on_host:
-        host = _tables_for([(C[acc], read_partition[acc]) for e in on_host for acc in e])
-        for e in on_host:
-            results[e] = _test_on_tables(C[e[1]], C[e[0]], of_edge[e][0], of_edge[e][1], host[id(read_partition[e[0]])], host[id(read_partition[e[1]])],
-                                         ccs_dict, max_phred_q_trusted)
-    return results
+                                         None if probs_c is None else probs_c[0], None if probs_t is None else probs_t[0], pending)
+
+
+# ---- Raghavan's bound on the device (isocon_raghavan_bound: csrc/pbound.hpp) ----
+# _raghavan_from_sums of all tests of a round in one call.  A lane returns a double only with the certificate that it is float() of the
+# 100-digit result (csrc/pbound_core.hpp); every other test -- sums outside the certified domain, where the decimals raise or
+# lose digits -- is evaluated by _raghavan_from_sums itself, in edge order.
+# tests: the pairs sent, certified: those that came back with the certificate, host_fallbacks: the tests then evaluated on the host
+BOUND_STATS = {"calls": 0, "tests": 0, "certified": 0, "host_fallbacks": 0, "kernel_ms": 0.0}
+BOUND_CALL_BYTES = 256 << 20          # the tests of a round are split over several calls only if their sums and answers exceed this
+
+
+def bounds_on_device_enabled():
+    """the bounds of a round's tests come from the device (isocon_raghavan_bound): the device tables are on and
+    ISOCON_DEBUG_VARIANT=stat_host_bound is not set"""
+    return device_tables_enabled() and not _variant_listed("stat_host_bound")
+
+
+class _PendingBound(object):
+    """stands in a test's tuple for the p-value that _resolve_bounds fills in: entry `at` of the round's collector"""
+    __slots__ = ("at",)
+
+    def __init__(self, at):
+        self.at = at
+
+
+def _device_bounds(m_sums, y_sums):
+    """one isocon_raghavan_bound call: (bounds float64, certified bool) for the tests' two sums; where certified, the bound has the bits of
+    _raghavan_from_sums(m_sum, y_sum), elsewhere it is 0.0"""
+    m = np.ascontiguousarray(m_sums, dtype=np.float64)
+    y = np.ascontiguousarray(y_sums, dtype=np.float64)
+    assert m.ndim == 1 and m.shape == y.shape
+    n = len(m)
+    bounds, certified = np.zeros(max(n, 1), dtype=np.float64), np.zeros(max(n, 1), dtype=np.uint8)
+    ms = ctypes.c_float(0.0)
+    _lib.check(_lib.lib().isocon_raghavan_bound(_ptr(m, _lib.f64p), _ptr(y, _lib.f64p), n, _ptr(bounds, _lib.f64p), _ptr(certified, _lib.u8p), ctypes.byref(ms)),
+               "isocon_raghavan_bound")
+    certified = certified[:n] != 0
+    BOUND_STATS["calls"] += 1
+    BOUND_STATS["tests"] += n
+    BOUND_STATS["certified"] += int(certified.sum())
+    BOUND_STATS["kernel_ms"] += ms.value
+    return bounds[:n], certified
+
+
+def _resolve_bounds(results, pending):
+    """the _PendingBound of every test in `results` replaced by its p-value: one _device_bounds call for the collector (several only above
+    BOUND_CALL_BYTES), then _raghavan_from_sums for the tests that came back without a certificate, in the order of `results`"""
+    if not pending:
+        return
+    per_call = max(1, BOUND_CALL_BYTES // 25)          # (16 bytes up, 9 bytes down per test)
+    bounds, certified = [], []
+    for lo in range(0, len(pending), per_call):
+        part = pending[lo:lo + per_call]
+        b, c = _device_bounds([float(m) for m, _ in part], [float(y) for _, y in part])
+        bounds.extend(b.tolist())
+        certified.extend(c.tolist())
+    for e, (variant_coords_t, p_value, n_support, used) in results.items():
+        if isinstance(p_value, _PendingBound):
+            if certified[p_value.at]:
+                p_value = bounds[p_value.at]
+            else:
+                BOUND_STATS["host_fallbacks"] += 1
+                p_value = _raghavan_from_sums(*pending[p_value.at])
+            results[e] = (variant_coords_t, p_value, n_support, used)
+    del pending[:]
 
 
 # ---- the variants of the edges on the device (isocon_edge_variants: csrc/edgevar.hpp) ----
@@ -852,11 +931,11 @@ def _test_on_tables(t_seq, c_seq, alignment_tc, alignment_ct, tab_c, tab_t, ccs_
 
 
 def _test_on_supporters(t_seq, variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c, tab_c, tab_t, sup_c, sup_t,
-                        ccs_dict=None, max_phred_q_trusted=None, codes_c=None, codes_t=None, probs_c=None, probs_t=None):
+                        ccs_dict=None, max_phred_q_trusted=None, codes_c=None, codes_t=None, probs_c=None, probs_t=None, pending=None):
     """The test of an edge once the supporting reads are known (sup_c / sup_t: ascending row indices into the tables of c / t, host
     or device tables alike): error probabilities per read and the bound.  With base qualities, device tables bring probs_c / probs_t
     (isocon_readtab_probability: one double per read, negative = not informative) or codes_c / codes_t (isocon_readtab_quality:
-    variants x reads); host tables compute theirs."""
+    variants x reads); host tables compute theirs.  pending: the round's collector of _raghavan_on_arrays."""
     n_support = len(sup_c) + len(sup_t)
     if len(variants) == 0:
         return variant_coords_t, 0.0, n_support, tab_c.n + tab_t.n
@@ -873,7 +952,7 @@ def _test_on_supporters(t_seq, variants, variant_coords_t, variant_coords_c, ali
         assert alive_c[sup_c].all() and alive_t[sup_t].all()
         slot_c = np.cumsum(alive_c) - 1                       # position of a read of c among the informative ones
         slot_t = int(alive_c.sum()) + np.cumsum(alive_t) - 1
-        return variant_coords_t, _raghavan_on_arrays(prob, np.concatenate([slot_c[sup_c], slot_t[sup_t]]) if n_support else None), n_support, len(prob)
+        return variant_coords_t, _raghavan_on_arrays(prob, np.concatenate([slot_c[sup_c], slot_t[sup_t]]) if n_support else None, pending), n_support, len(prob)
     # error probabilities per read, t's reads first (functions.get_read_errors / get_empirical_error_probabilities)
     n_reads = tab_t.n + tab_c.n
     if n_reads == 0:
@@ -893,12 +972,13 @@ def _test_on_supporters(t_seq, variants, variant_coords_t, variant_coords_c, ali
         elif v_type == "D":
             prob *= np.minimum(0.5, p_D * u_v)
     prob[prob >= 1.0] = 0.99999
-    return variant_coords_t, _raghavan_on_arrays(prob, np.concatenate([tab_t.n + sup_c, sup_t]) if n_support else None), n_support, n_reads
+    return variant_coords_t, _raghavan_on_arrays(prob, np.concatenate([tab_t.n + sup_c, sup_t]) if n_support else None, pending), n_support, n_reads
 
 
-def _raghavan_on_arrays(prob, supporters):
+def _raghavan_on_arrays(prob, supporters, pending=None):
     """raghavan_upper_pvalue_bound for probabilities in dict order and the indices of the supporting reads (in the order of
-    functions.get_support): logarithms with math.log per distinct probability, sums left to right like the reference's."""
+    functions.get_support): logarithms with math.log per distinct probability, sums left to right like the reference's.  pending: a list
+    that takes (m_sum, y_sum) in place of the evaluation -- a _PendingBound comes back, for _resolve_bounds."""
     assert prob.max() <= 1.0 and prob.min() > 0.0
     uniq, inv = np.unique(prob, return_inverse=True)
     logs = [-math.log(p, 10) for p in uniq.tolist()]
@@ -908,6 +988,9 @@ def _raghavan_on_arrays(prob, supporters):
     weight = w_u[inv]
     m_sum = sum((w_u * uniq)[inv].tolist())
     y_sum = sum(weight[supporters].tolist()) if supporters is not None else 0
+    if pending is not None:
+        pending.append((m_sum, y_sum))
+        return _PendingBound(len(pending) - 1)
     return _raghavan_from_sums(m_sum, y_sum)
 
 

@@ -1,6 +1,7 @@
 """Wall time of the whole pipeline (find_candidate_transcripts + stat_filter_candidates) on synthetic CCS reads, with a
-breakdown of the statistical-test phase.  Usage: python scripts/time_full_pipeline.py [n_reads] [length] [isoforms] [ont|ccs] [fastq]"""
-import cProfile, os, pstats, sys, tempfile, time
+breakdown of the statistical-test phase.  Usage: python scripts/time_full_pipeline.py [n_reads] [length] [isoforms] [ont|ccs] [fastq]
+The SHA-256 of every result file is printed; ISOCON_KEEP_RESULTS=<directory> also keeps copies of them there (for a cmp between runs)."""
+import cProfile, hashlib, os, pstats, shutil, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from isocon_amd import synth
 from isocon_amd import isocon_get_candidates as IGC
@@ -43,4 +44,12 @@ with tempfile.TemporaryDirectory() as tmp:
     from isocon_amd import hypothesis_test_module as H
     print("device read tables: %s" % H.DEVICE_STATS)
     print("edge variants on the device (isocon_edge_variants; none under ISOCON_DEBUG_VARIANT=stat_host_variants): %s" % H.EDGE_VARIANT_STATS, flush=True)
+    print("bounds on the device (isocon_raghavan_bound; none under ISOCON_DEBUG_VARIANT=stat_host_bound): %s" % H.BOUND_STATS, flush=True)
+    results = sorted(f for f in os.listdir(tmp) if f in ("final_candidates.fa", "cluster_info.tsv") or f.startswith("p_values_"))
+    for f in results:          # the result files: their digests, and copies under $ISOCON_KEEP_RESULTS for a cmp between runs
+        with open(os.path.join(tmp, f), "rb") as fh:
+            print("sha256 %s %s" % (hashlib.sha256(fh.read()).hexdigest(), f))
+        if os.environ.get("ISOCON_KEEP_RESULTS"):
+            os.makedirs(os.environ["ISOCON_KEEP_RESULTS"], exist_ok=True)
+            shutil.copy(os.path.join(tmp, f), os.environ["ISOCON_KEEP_RESULTS"])
     pstats.Stats(pr).sort_stats("cumulative").print_stats(28)
