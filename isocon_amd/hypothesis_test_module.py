@@ -18,9 +18,11 @@ looked up on the same read tables, and on the device tables the lanes multiply t
 with a certificate per test that its double is float() of the decimal result; a test without it goes through _raghavan_from_sums."""
 from __future__ import annotations
 
+import collections
 import ctypes
 import decimal
 import math
+import operator
 import os
 
 import numpy as np
@@ -28,6 +30,27 @@ import numpy as np
 from . import _lib
 from . import functions
 from . import SW_alignment_module as SWM
+
+
+# An edge's variants, where they lie on t and on c (the reference's variant_coords_t / _c), and per variant the snippet of c's row under t's
+# coordinate and of t's row under c's (alignment_c_to_t / alignment_t_to_c); a query of the device tables (_pack_queries).  Equal to plain tuples.
+_EdgeVariants = collections.namedtuple("_EdgeVariants", "variants coords_t coords_c c_to_t t_to_c")
+_Query = collections.namedtuple("_Query", "table kind coords snippets n_rows")
+
+
+# What differs between the reads of c and of t in a test (functions.get_support, get_read_ccs_probabilities_c / _t): the kind of their device queries;
+# getters on an _EdgeVariants for their variant coordinates, for the snippets of a support query (none: the reads are compared with their candidate's
+# row) and for the other sequence's snippets of a quality query; the variant type at which the other sequence's window lies a column to the left; by
+# variant type, where a read that shows the other sequence has its judged base among the read bases seen (-1 unless listed).  _SIDES: by query kind.
+_Side = collections.namedtuple("_Side", "kind coords support_snippets quality_snippets shifted_type coord_when_other")
+_SIDE_C = _Side(0, operator.attrgetter("coords_c"), lambda ev: None, operator.attrgetter("t_to_c"), "D", {"I": 0})
+_SIDE_T = _Side(1, operator.attrgetter("coords_t"), operator.attrgetter("c_to_t"), operator.attrgetter("c_to_t"), "I", {"D": 0, "I": -2})
+_SIDES = (_SIDE_C, _SIDE_T)
+
+
+def _other_window(shifted_type, v_type, u_v):
+    """(columns before, columns after) a variant's position in which a read shows the other sequence's snippet"""
+    return (2, u_v) if v_type == shifted_type else (1, u_v + 1)
 
 
 def _clamp(a, hi):
@@ -58,28 +81,15 @@ class _ReadTable(object):
         """reads whose row equals the candidate's row over every variant window (get_support, reads of c)"""
         ok = np.ones(self.n, dtype=bool)
         for i, (_, _, u_v) in variant_coords.items():
-            pos = self.column_of(i, ok)
-            for w in range(-1, u_v + 1):
-                col = pos + w
-                valid = (col >= 0) & (col < self.len)
-                ok &= ~(valid & self.diff[_clamp(self.off0 + col, self.total - 1)])
+            ok &= self.own_window_equal(self.column_of(i, ok), u_v)
         return ok
 
     def show_snippets(self, variant_coords, snippets):
         """reads that show the other sequence's snippet at every variant (get_support, reads of t)"""
         ok = np.ones(self.n, dtype=bool)
         for i, (v_type, _, u_v) in variant_coords.items():
-            pos = self.column_of(i, ok)
-            snippet = np.frombuffer(snippets[i].encode("ascii"), dtype=np.uint8)
-            before, after = (2, u_v) if v_type == "I" else (1, u_v + 1)
-            lo = np.maximum(0, pos - before)
-            hi = np.minimum(self.len, pos + after)
-            match = np.maximum(hi - lo, 0) == len(snippet)
-            for j in range(len(snippet)):
-                match &= self.read[_clamp(self.off0 + lo + j, self.total - 1)] == snippet[j]
-            ok &= match
+            ok &= self.window_equals(self.column_of(i, ok), *_other_window(_SIDE_T.shifted_type, v_type, u_v), snippets[i])
         return ok
-
 
     # ---- pieces of the quality-based probabilities (functions._ccs_probabilities), per read and per variant ----
     def own_window_equal(self, pos, u_v):
@@ -115,17 +125,9 @@ class _ReadTable(object):
     def qualities(self, ccs_dict):
         """(flat qualities, offset of every read's record, record length, start of the read inside its record)"""
         if getattr(self, "_qual_of", None) is not ccs_dict:
-            recs = [ccs_dict[acc] for acc in self.accs]
-            lens = np.fromiter((len(r.qual) for r in recs), dtype=np.int64, count=self.n)
-            off = np.zeros(self.n + 1, dtype=np.int64)
-            np.cumsum(lens, out=off[1:])
-            for r in recs:                                  # the record's quality list as an array, made once per record
-                if getattr(r, "_qual_np_of", None) is not r.qual:
-                    r._qual_np, r._qual_np_of = np.asarray(r.qual, dtype=np.int64), r.qual
-            flat = np.concatenate([r._qual_np for r in recs]) if recs else np.zeros(0, dtype=np.int64)
-            reads = self.read_rows_without_gaps()
-            start = np.fromiter((r.seq.index(x) for r, x in zip(recs, reads)), dtype=np.int64, count=self.n)
-            self._qual = (flat, off[:-1], np.fromiter((len(r.seq) for r in recs), dtype=np.int64, count=self.n), start)
+            recs = [ccs_dict[acc] for acc in self.accs]          # (KeyError, and ValueError from _read_starts: the caller's)
+            flat, off = _quality_arrays(recs)
+            self._qual = (flat, off[:-1], np.fromiter((len(r.seq) for r in recs), dtype=np.int64, count=self.n), _read_starts(recs, self.read_rows_without_gaps()))
             self._qual_of = ccs_dict
         return self._qual
 
@@ -133,6 +135,21 @@ class _ReadTable(object):
         raw = self.read.tobytes().decode("ascii")
         o = self.off0.tolist() + [self.total]
         return [raw[o[r]:o[r + 1]].replace("-", "") for r in range(self.n)]
+
+
+def _quality_arrays(recs):
+    """(the records' quality lists as one flat int64 array, their len(recs) + 1 offsets in it); a record keeps its array (_qual_np)"""
+    for r in recs:                                  # the record's quality list as an array, made once per record
+        if getattr(r, "_qual_np_of", None) is not r.qual:
+            r._qual_np, r._qual_np_of = np.asarray(r.qual, dtype=np.int64), r.qual
+    off = np.zeros(len(recs) + 1, dtype=np.int64)
+    np.cumsum([len(r._qual_np) for r in recs], out=off[1:])
+    return (np.concatenate([r._qual_np for r in recs]) if recs else np.zeros(0, dtype=np.int64)), off
+
+
+def _read_starts(recs, reads):
+    """where each read (without gaps) starts in its record's sequence; ValueError for a record that does not hold its read"""
+    return np.fromiter((r.seq.index(x) for r, x in zip(recs, reads)), dtype=np.int64, count=len(recs))
 
 
 # What one read says at one variant, as a byte (csrc/readtab_core.hpp rt_quality_code): its quality 0 .. 93 there, or
@@ -144,10 +161,7 @@ def _quality_codes_on_table(tab, i, v_type, u_v, alive, other_snippet, ccs_dict,
     flat, qoff, rec_len, rec_start = tab.qualities(ccs_dict)
     pos = tab.column_of(i, alive)
     shows_own = tab.own_window_equal(pos, u_v)
-    if v_type == shifted_type:
-        shows_other = tab.window_equals(pos, 2, u_v, other_snippet)
-    else:
-        shows_other = tab.window_equals(pos, 1, u_v + 1, other_snippet)
+    shows_other = tab.window_equals(pos, *_other_window(shifted_type, v_type, u_v), other_snippet)
     seen = tab.read_bases_upto(pos)
     read_coord = np.where(shows_own, seen - 1, seen + coord_when_other.get(v_type, -1))
     coord = rec_start + read_coord                     # CCS.read_aln_to_ccs_coord
@@ -219,17 +233,18 @@ def _ccs_probabilities_from_codes(n, variant_coords, code_of, ratios, max_phred_
     return alive, prob
 
 
-def _ccs_probabilities_on_table(tab, variant_coords, other_snippets, ccs_dict, ratios, max_phred_q_trusted, shifted_type, coord_when_other, codes=None, probs=None):
-    """_ccs_probabilities_from_codes for a table: a device table brings its codes (variants x reads) -- or the finished products (probs:
-    one double per read, negative = not informative; isocon_readtab_probability) --, a host table computes them"""
-    if probs is not None:
-        alive = probs >= 0
-        assert ((probs[alive] > 0.0) & (probs[alive] < 1.0)).all()
-        return alive, probs
+def _ccs_probabilities_on_table(side, work, ev, ccs_dict, ratios, max_phred_q_trusted):
+    """_ccs_probabilities_from_codes for the table of one side (work: its _SideWork) of the edge ev: a device table brings the finished products
+    (_device_probability's answer: one double per read, negative = not informative) or its codes (_device_quality's), a host table computes its codes"""
+    if work.probs is not None:
+        alive = work.probs >= 0
+        assert ((work.probs[alive] > 0.0) & (work.probs[alive] < 1.0)).all()
+        return alive, work.probs
+    tab, codes, variant_coords, other_snippets = work.tab, work.codes, side.coords(ev), side.quality_snippets(ev)
     if codes is not None:
         return _ccs_probabilities_from_codes(tab.n, variant_coords, lambda v, i, v_type, u_v, alive: codes[v], ratios, max_phred_q_trusted)
     return _ccs_probabilities_from_codes(tab.n, variant_coords, lambda v, i, v_type, u_v, alive: _quality_codes_on_table(
-        tab, i, v_type, u_v, alive, other_snippets[i], ccs_dict, shifted_type, coord_when_other), ratios, max_phred_q_trusted)
+        tab, i, v_type, u_v, alive, other_snippets[i], ccs_dict, side.shifted_type, side.coord_when_other), ratios, max_phred_q_trusted)
 
 
 def _variants_of(aln_t, aln_c):
@@ -334,10 +349,15 @@ _TABLES = {}        # id(read-alignment dict) -> (the dict, its alignment tuples
 _DEVICE_TABLES = {}     # the same for the tables kept on the device (_DeviceTable)
 
 
+def _device_sets():
+    """the table sets (_DeviceSet) of the cached device tables, each once"""
+    return {id(hit[2].set): hit[2].set for hit in _DEVICE_TABLES.values()}.values()
+
+
 def clear_tables():
     _TABLES.clear()
-    for tab in {id(hit[2].set): hit[2].set for hit in _DEVICE_TABLES.values()}.values():
-        tab.free()
+    for dset in _device_sets():
+        dset.free()
     _DEVICE_TABLES.clear()
 
 
@@ -378,32 +398,43 @@ def _tables_for(wanted, cache=None, build=None):
 DEVICE_STATS = {"create_calls": 0, "rows_uploaded": 0, "support_calls": 0, "queries": 0, "quality_attach_calls": 0, "quality_calls": 0, "probability_calls": 0,
                 "kernel_ms": 0.0}
 _HAS_DEVICE = None
+_Routes = collections.namedtuple("_Routes", "tables variants probabilities bounds")
 
 
-def _variant_listed(name):
-    """is `name` listed in ISOCON_DEBUG_VARIANT (name[=value],name,...)?"""
-    return any(item.split("=")[0] == name for item in os.environ.get("ISOCON_DEBUG_VARIANT", "").split(","))
+def _routes():
+    """Which parts of a round run on the device, from ISOCON_DEBUG_VARIANT (name[=value],name,...) and the device count, for a round to ask
+    once; what each switch means stands with the *_enabled() function over it below."""
+    global _HAS_DEVICE
+    listed = {item.split("=")[0] for item in os.environ.get("ISOCON_DEBUG_VARIANT", "").split(",")}
+    if _HAS_DEVICE is None and "stat_host_tables" not in listed:
+        _HAS_DEVICE = _lib.load().isocon_device_count() > 0
+    tables = "stat_host_tables" not in listed and _HAS_DEVICE
+    return _Routes(tables, *(tables and name not in listed for name in ("stat_host_variants", "stat_host_prob", "stat_host_bound")))
 
 
 def device_tables_enabled():
     """the tests of a round go through the device tables: a GPU is there and ISOCON_DEBUG_VARIANT=stat_host_tables is not set"""
-    global _HAS_DEVICE
-    if _variant_listed("stat_host_tables"):
-        return False
-    if _HAS_DEVICE is None:
-        _HAS_DEVICE = _lib.load().isocon_device_count() > 0
-    return _HAS_DEVICE
+    return _routes().tables
+
+
+def edge_variants_on_device_enabled():
+    """the variants of a round's edges come from the device (isocon_edge_variants): the device tables are on and stat_host_variants is not set"""
+    return _routes().variants
 
 
 def probabilities_on_device_enabled():
-    """with base qualities the reads' probabilities come from the device (isocon_readtab_probability) and not from its code bytes:
-    the device tables are on and ISOCON_DEBUG_VARIANT=stat_host_prob is not set"""
-    return device_tables_enabled() and not _variant_listed("stat_host_prob")
+    """with base qualities the reads' probabilities come from isocon_readtab_probability, not from the code bytes: the device tables are on and stat_host_prob is not set"""
+    return _routes().probabilities
+
+
+def bounds_on_device_enabled():
+    """the bounds of a round's tests come from the device (isocon_raghavan_bound): the device tables are on and stat_host_bound is not set"""
+    return _routes().bounds
 
 
 def device_table_bytes():
     """device memory held by the cached table sets"""
-    return sum(s.bytes for s in {id(hit[2].set): hit[2].set for hit in _DEVICE_TABLES.values()}.values())
+    return sum(s.bytes for s in _device_sets())
 
 
 def _ptr(a, typ):
@@ -429,20 +460,16 @@ class _DeviceSet(object):
         n = len(self.accs)
         try:
             recs = [ccs_dict[acc] for acc in self.accs]
-            start = np.fromiter((r.seq.index(row.replace("-", "")) for r, row in zip(recs, self.read_rows)), dtype=np.int64, count=n)
+            start = _read_starts(recs, [row.replace("-", "") for row in self.read_rows])
         except (KeyError, ValueError):
             return False
-        for r in recs:                                  # the record's quality list as an array, made once per record
-            if getattr(r, "_qual_np_of", None) is not r.qual:
-                r._qual_np, r._qual_np_of = np.asarray(r.qual, dtype=np.int64), r.qual
+        flat, off = _quality_arrays(recs)
         if any(len(r.seq) != len(r._qual_np) for r in recs):
             return False
-        flat = np.concatenate([r._qual_np for r in recs]) if recs else np.zeros(0, dtype=np.int64)
         if len(flat) and (flat.min() < 0 or flat.max() > 93):
             return False
-        qual_ptr = np.zeros(n + 1, dtype=np.uint64)
-        np.cumsum(np.fromiter((len(r._qual_np) for r in recs), dtype=np.uint64, count=n), out=qual_ptr[1:])
         qual = flat.astype(np.uint8) if len(flat) else np.zeros(1, dtype=np.uint8)
+        qual_ptr = off.astype(np.uint64)
         rec_start = start.astype(np.uint32) if n else np.zeros(1, dtype=np.uint32)
         ms = ctypes.c_float(0.0)
         _lib.check(_lib.lib().isocon_readtab_set_qualities(self.handle, _ptr(qual, _lib.u8p), _ptr(qual_ptr, _lib.u64p), _ptr(rec_start, _lib.u32p), ctypes.byref(ms)),
@@ -545,21 +572,26 @@ def _rows_of_bits(words, n_rows):
     return np.flatnonzero(np.unpackbits(words.view(np.uint8), bitorder="little")[:n_rows])
 
 
+def _query_call(entry, handle, packed, *own):
+    """one call of a query entry of the device tables (isocon_readtab_support / _quality / _probability): the set, the number of queries and
+    q_table .. snip_bytes of _pack_queries, which all three take alike, then the entry's own arrays as (array, pointer type); adds the kernel time"""
+    shared = zip(packed, (_lib.u32p, _lib.u8p, _lib.u64p, _lib.i32p, _lib.i32p, _lib.u8p, _lib.u64p, _lib.u8p))
+    ms = ctypes.c_float(0.0)
+    _lib.check(getattr(_lib.lib(), entry)(handle, len(packed[0]), *[_ptr(a, t) for a, t in list(shared) + list(own)], ctypes.byref(ms)), entry)
+    DEVICE_STATS["kernel_ms"] += ms.value
+
+
 def _device_support(handle, queries):
     """one isocon_readtab_support call: the supporting rows (ascending indices into its table) of every query of _pack_queries"""
     if not queries:
         return []
-    q_table, q_kind, var_ptr, var_pos, var_u, var_type, snip_ptr, snip_bytes, bits_ptr = _pack_queries(queries)
+    packed = _pack_queries(queries)
+    bits_ptr = packed[8]
     bits = np.zeros(max(int(bits_ptr[-1]), 1), dtype=np.uint64)
     count = np.zeros(len(queries), dtype=np.uint32)
-    ms = ctypes.c_float(0.0)
-    _lib.check(_lib.lib().isocon_readtab_support(handle, len(queries), _ptr(q_table, _lib.u32p), _ptr(q_kind, _lib.u8p), _ptr(var_ptr, _lib.u64p),
-                                                 _ptr(var_pos, _lib.i32p), _ptr(var_u, _lib.i32p), _ptr(var_type, _lib.u8p), _ptr(snip_ptr, _lib.u64p),
-                                                 _ptr(snip_bytes, _lib.u8p), _ptr(bits_ptr, _lib.u64p), _ptr(bits, _lib.u64p), _ptr(count, _lib.u32p),
-                                                 ctypes.byref(ms)), "isocon_readtab_support")
+    _query_call("isocon_readtab_support", handle, packed, (bits_ptr, _lib.u64p), (bits, _lib.u64p), (count, _lib.u32p))
     DEVICE_STATS["support_calls"] += 1
     DEVICE_STATS["queries"] += len(queries)
-    DEVICE_STATS["kernel_ms"] += ms.value
     out = []
     for q, (_, _, _, _, n_rows) in enumerate(queries):
         sup = _rows_of_bits(bits[int(bits_ptr[q]):int(bits_ptr[q + 1])], n_rows) if count[q] else np.zeros(0, dtype=np.int64)
@@ -572,16 +604,11 @@ def _device_quality(handle, queries):
     """one isocon_readtab_quality call: the code bytes (variants x rows, uint8) of every query of _pack_queries (snippets for both kinds)"""
     if not queries:
         return []
-    q_table, q_kind, var_ptr, var_pos, var_u, var_type, snip_ptr, snip_bytes, _ = _pack_queries(queries)
     code_ptr = np.zeros(len(queries) + 1, dtype=np.uint64)
     np.cumsum(np.asarray([len(coords) * n_rows for _, _, coords, _, n_rows in queries], dtype=np.uint64), out=code_ptr[1:])
     codes = np.zeros(max(int(code_ptr[-1]), 1), dtype=np.uint8)
-    ms = ctypes.c_float(0.0)
-    _lib.check(_lib.lib().isocon_readtab_quality(handle, len(queries), _ptr(q_table, _lib.u32p), _ptr(q_kind, _lib.u8p), _ptr(var_ptr, _lib.u64p),
-                                                 _ptr(var_pos, _lib.i32p), _ptr(var_u, _lib.i32p), _ptr(var_type, _lib.u8p), _ptr(snip_ptr, _lib.u64p),
-                                                 _ptr(snip_bytes, _lib.u8p), _ptr(code_ptr, _lib.u64p), _ptr(codes, _lib.u8p), ctypes.byref(ms)), "isocon_readtab_quality")
+    _query_call("isocon_readtab_quality", handle, _pack_queries(queries), (code_ptr, _lib.u64p), (codes, _lib.u8p))
     DEVICE_STATS["quality_calls"] += 1
-    DEVICE_STATS["kernel_ms"] += ms.value
     return [codes[int(code_ptr[q]):int(code_ptr[q + 1])].reshape(len(coords), n_rows) for q, (_, _, coords, _, n_rows) in enumerate(queries)]
 
 
@@ -599,85 +626,92 @@ def _device_probability(handle, queries, ratios, max_phred_q_trusted):
         while hi < len(queries) and (rows + queries[hi][4]) * 8 <= PROBABILITY_CALL_BYTES:
             rows += queries[hi][4]
             hi += 1
-        out.extend(_device_probability_call(handle, queries[lo:hi], ratios[lo:hi], max_phred_q_trusted))
+        prob_ptr = np.zeros(hi - lo + 1, dtype=np.uint64)
+        np.cumsum(np.asarray([query[4] for query in queries[lo:hi]], dtype=np.uint64), out=prob_ptr[1:])
+        probs = np.zeros(max(int(prob_ptr[-1]), 1), dtype=np.float64)
+        status = np.zeros(hi - lo, dtype=np.uint32)
+        q_ratios = np.ascontiguousarray(ratios[lo:hi], dtype=np.float64).reshape(hi - lo, 3)
+        _query_call("isocon_readtab_probability", handle, _pack_queries(queries[lo:hi]), (q_ratios, _lib.f64p), (_p_of_quality(max_phred_q_trusted), _lib.f64p),
+                    (prob_ptr, _lib.u64p), (probs, _lib.f64p), (status, _lib.u32p))
+        DEVICE_STATS["probability_calls"] += 1
+        ptr = prob_ptr.tolist()
+        out.extend((probs[ptr[q]:ptr[q + 1]], s) for q, s in enumerate(status.tolist()))
         lo = hi
     return out
-
-
-def _device_probability_call(handle, queries, ratios, max_phred_q_trusted):
-    q_table, q_kind, var_ptr, var_pos, var_u, var_type, snip_ptr, snip_bytes, _ = _pack_queries(queries)
-    prob_ptr = np.zeros(len(queries) + 1, dtype=np.uint64)
-    np.cumsum(np.asarray([n_rows for _, _, _, _, n_rows in queries], dtype=np.uint64), out=prob_ptr[1:])
-    probs = np.zeros(max(int(prob_ptr[-1]), 1), dtype=np.float64)
-    status = np.zeros(len(queries), dtype=np.uint32)
-    q_ratios = np.ascontiguousarray(ratios, dtype=np.float64).reshape(len(queries), 3)
-    base = _p_of_quality(max_phred_q_trusted)
-    ms = ctypes.c_float(0.0)
-    _lib.check(_lib.lib().isocon_readtab_probability(handle, len(queries), _ptr(q_table, _lib.u32p), _ptr(q_kind, _lib.u8p), _ptr(var_ptr, _lib.u64p),
-                                                     _ptr(var_pos, _lib.i32p), _ptr(var_u, _lib.i32p), _ptr(var_type, _lib.u8p), _ptr(snip_ptr, _lib.u64p),
-                                                     _ptr(snip_bytes, _lib.u8p), _ptr(q_ratios, _lib.f64p), _ptr(base, _lib.f64p), _ptr(prob_ptr, _lib.u64p),
-                                                     _ptr(probs, _lib.f64p), _ptr(status, _lib.u32p), ctypes.byref(ms)), "isocon_readtab_probability")
-    DEVICE_STATS["probability_calls"] += 1
-    DEVICE_STATS["kernel_ms"] += ms.value
-    ptr, status = prob_ptr.tolist(), status.tolist()
-    return [(probs[ptr[q]:ptr[q + 1]], status[q]) for q in range(len(queries))]
 
 
 def _in_range(coords, ref_len):
     return all(-ref_len <= i < ref_len for i in coords)
 
 
-def _tests_on_device(live, of_edge, C, read_partition, ccs_dict=None, max_phred_q_trusted=None, variants_of=None):
-    """{edge: (variant_coords_t, p_value, supporting reads, reads used)} for the edges of a round: supporters and error counts from the
-    device tables, one support call per table set; with base qualities (ccs_dict) also every read's probability (or, under
-    ISOCON_DEBUG_VARIANT=stat_host_prob, its quality code at every variant for the host to multiply up), one call per table set.  An edge
-    for which the device reports that something is to be raised goes through the codes, where it is raised.  An edge with a variant coordinate that the per-read statement cannot index stays on the host tables,
-    where it raises as it always did; so does an edge of a table set whose qualities cannot be attached.  variants_of: {edge: the tuple
-    of _edge_variants} where the caller has them (_edge_variants_on_device); of_edge[e], the two gapped alignments, is then looked at
-    only for the edges that stay on the host tables (_LazyAlignments).  The bounds of the edges on the device tables follow in one call after
-    their loop (_resolve_bounds) unless ISOCON_DEBUG_VARIANT=stat_host_bound is set."""
+class _SideWork(object):
+    """One side of one edge through a round -- the reads of c, or of t: their table (host or device) and the supporting rows (ascending
+    indices into it).  On the device tables also its queries (quality_query and the edge's ratios: None where the test looks at no quality)
+    and what the device said about the qualities: probs and status (_device_probability) or codes (_device_quality); neither: a host table computes its own."""
+    __slots__ = ("tab", "supporters", "codes", "probs", "status", "support_query", "quality_query", "ratios")
+
+    def __init__(self, tab, supporters=None, codes=None, probs=None):
+        self.tab, self.supporters, self.codes, self.probs = tab, supporters, codes, probs
+        self.status = self.support_query = self.quality_query = self.ratios = None
+
+
+def _tests_on_device(live, of_edge, C, read_partition, ccs_dict=None, max_phred_q_trusted=None, variants_of=None, routes=None):
+    """{edge: (variant_coords_t, p_value, supporting reads, reads used)} for the edges of a round: supporters and error counts from the device tables, one
+    support call per table set; with base qualities (ccs_dict) also every read's probability (or, under ISOCON_DEBUG_VARIANT=stat_host_prob, its quality
+    code at every variant for the host to multiply up), one call per table set. An edge for which the device reports that something is to be raised goes
+    through the codes, where it is raised. An edge with a variant coordinate that the per-read statement cannot index stays on the host tables, where it
+    raises; so does an edge of a table set whose qualities cannot be attached. variants_of: {edge: its _edge_variants} where the caller has them
+    (_edge_variants_on_device); of_edge[e], the two gapped alignments, is then looked at only for the edges that stay on the host tables
+    (_LazyAlignments). The bounds of these edges follow in one call after their loop (_resolve_bounds) if routes, the round's _routes(), says so."""
+    routes = _routes() if routes is None else routes
     prepared, on_host = {}, []
     for e in live:
         c_acc, t_acc = e
         ev = variants_of[e] if variants_of is not None else _edge_variants(C[t_acc], C[c_acc], of_edge[e][0], of_edge[e][1])
-        if _in_range(ev[2], len(C[c_acc])) and _in_range(ev[1], len(C[t_acc])):
+        ev = ev if type(ev) is _EdgeVariants else _EdgeVariants._make(ev)          # (a plain tuple from a caller of its own)
+        if _in_range(ev.coords_c, len(C[c_acc])) and _in_range(ev.coords_t, len(C[t_acc])):
             prepared[e] = ev
         else:
             on_host.append(e)
     tables = _tables_for([(C[acc], read_partition[acc]) for e in prepared for acc in e], _DEVICE_TABLES, _build_device_tables)
-    if ccs_dict:
-        for e in list(prepared):
-            if not all(tables[id(read_partition[acc])].set.attach_qualities(ccs_dict) for acc in e):
-                del prepared[e]
-                on_host.append(e)
-    on_device_prob = bool(ccs_dict) and probabilities_on_device_enabled()
-    by_set = {}          # id(set) -> (set, its support queries, where each answer goes, its quality queries, where each answer goes, their ratios)
+    on_device_prob = bool(ccs_dict) and routes.probabilities
+    work, by_set = {}, {}          # edge -> (its variants, its c side, its t side); id(table set) -> the sides on it, in edge order
     for e, ev in prepared.items():
-        tab_c, tab_t = tables[id(read_partition[e[0]])], tables[id(read_partition[e[1]])]
-        ratios = _error_ratios(tab_c, tab_t) if on_device_prob and len(ev[0]) > 0 else None
-        for side, tab, kind, coords, snippets, others in ((0, tab_c, 0, ev[2], None, ev[4]), (1, tab_t, 1, ev[1], ev[3], ev[3])):
-            group = by_set.setdefault(id(tab.set), (tab.set, [], [], [], [], []))
-            group[1].append((tab.k, kind, coords, snippets, tab.n))
-            group[2].append((e, side))
-            if ccs_dict and len(ev[0]) > 0:          # (no variants: the test looks at no quality)
-                group[3].append((tab.k, kind, coords, others, tab.n))
-                group[4].append((e, side))
-                group[5].append(ratios)
-    supporters, codes, probs, asked = {}, {}, {}, {}
-    for dset, queries, where, quality_queries, quality_where, quality_ratios in by_set.values():
-        for key, sup in zip(where, _device_support(dset.handle, queries)):
-            supporters[key] = sup
-        if on_device_prob and quality_queries:
-            for key, query, answer in zip(quality_where, quality_queries, _device_probability(dset.handle, quality_queries, quality_ratios, max_phred_q_trusted)):
-                probs[key], asked[key] = answer, (dset.handle, query)
+        sides = [_SideWork(tables[id(read_partition[acc])]) for acc in e]
+        if ccs_dict and not all(item.tab.set.attach_qualities(ccs_dict) for item in sides):
+            on_host.append(e)
+            continue
+        work[e] = (ev, sides[0], sides[1])
+        with_qualities = bool(ccs_dict) and len(ev.variants) > 0          # (no variants: the test looks at no quality)
+        ratios = _error_ratios(sides[0].tab, sides[1].tab) if on_device_prob and with_qualities else None
+        for side, item in zip(_SIDES, sides):
+            tab, coords = item.tab, side.coords(ev)
+            item.support_query = _Query(tab.k, side.kind, coords, side.support_snippets(ev), tab.n)
+            if with_qualities:
+                item.quality_query, item.ratios = _Query(tab.k, side.kind, coords, side.quality_snippets(ev), tab.n), ratios
+            by_set.setdefault(id(item.tab.set), []).append(item)
+    for batch in by_set.values():
+        handle = batch[0].tab.set.handle
+        for item, sup in zip(batch, _device_support(handle, [item.support_query for item in batch])):
+            item.supporters = sup
+        asking = [item for item in batch if item.quality_query is not None]
+        queries = [item.quality_query for item in asking]
+        if on_device_prob and asking:
+            for item, (probs, status) in zip(asking, _device_probability(handle, queries, [item.ratios for item in asking], max_phred_q_trusted)):
+                item.probs, item.status = probs, status
             DEVICE_STATS["quality_calls"] += 1
         else:
-            for key, code in zip(quality_where, _device_quality(dset.handle, quality_queries)):
-                codes[key] = code
+            for item, codes in zip(asking, _device_quality(handle, queries)):
+                item.codes = codes
     results = {}
-    pending = [] if bounds_on_device_enabled() else None          # (m_sum, y_sum) of the tests whose bound is still to come
+    pending = [] if routes.bounds else None          # (m_sum, y_sum) of the tests whose bound is still to come: the p-values are then _PendingBound
     try:
-        _tests_of_prepared(results, pending, prepared, probs, asked, codes, supporters, tables, C, read_partition, ccs_dict, max_phred_q_trusted)
+        for e, (ev, work_c, work_t) in work.items():          # (in edge order)
+            if work_c.status or work_t.status:
+                # something is to be raised on this edge: its code bytes, and the host's loop over them raises it (c's reads before t's)
+                for item in (work_c, work_t):
+                    item.codes, item.probs = _device_quality(item.tab.set.handle, [item.quality_query])[0], None
+            results[e] = _test_on_supporters(C[e[1]], ev, work_c, work_t, ccs_dict, max_phred_q_trusted, pending)
     except (Exception, SystemExit):          # (what the tests themselves raise -- SystemExit is one of them --, not an interrupt)
         _resolve_bounds(results, pending)          # the bound of an earlier edge that is to raise raises first, as it did
         raise
@@ -690,23 +724,6 @@ def _tests_on_device(live, of_edge, C, read_partition, ccs_dict=None, max_phred_
     return results
 
 
-def _tests_of_prepared(results, pending, prepared, probs, asked, codes, supporters, tables, C, read_partition, ccs_dict, max_phred_q_trusted):
-    """the loop of _tests_on_device over the edges on the device tables, in edge order; with `pending` the p-values are _PendingBound"""
-    for e, ev in prepared.items():
-        variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c = ev
-        probs_c, probs_t = probs.get((e, 0)), probs.get((e, 1))
-        if probs_c is not None and (probs_c[1] or probs_t[1]):
-            # something is to be raised on this edge: its code bytes, and the host's loop over them raises it (c's reads before t's)
-            for side in (0, 1):
-                handle, query = asked[(e, side)]
-                codes[(e, side)] = _device_quality(handle, [query])[0]
-            probs_c = probs_t = None
-        results[e] = _test_on_supporters(C[e[1]], variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c,
-                                         tables[id(read_partition[e[0]])], tables[id(read_partition[e[1]])], supporters[(e, 0)], supporters[(e, 1)],
-                                         ccs_dict, max_phred_q_trusted, codes.get((e, 0)), codes.get((e, 1)),
-                                         None if probs_c is None else probs_c[0], None if probs_t is None else probs_t[0], pending)
-
-
 # ---- Raghavan's bound on the device (isocon_raghavan_bound: csrc/pbound.hpp) ----
 # _raghavan_from_sums of all tests of a round in one call.  A lane returns a double only with the certificate that it is float() of the
 # 100-digit result (csrc/pbound_core.hpp, DESIGN.md 4.7); every other test -- sums outside the certified domain, where the decimals raise or
@@ -714,12 +731,6 @@ def _tests_of_prepared(results, pending, prepared, probs, asked, codes, supporte
 # tests: the pairs sent, certified: those that came back with the certificate, host_fallbacks: the tests then evaluated on the host
 BOUND_STATS = {"calls": 0, "tests": 0, "certified": 0, "host_fallbacks": 0, "kernel_ms": 0.0}
 BOUND_CALL_BYTES = 256 << 20          # the tests of a round are split over several calls only if their sums and answers exceed this
-
-
-def bounds_on_device_enabled():
-    """the bounds of a round's tests come from the device (isocon_raghavan_bound): the device tables are on and
-    ISOCON_DEBUG_VARIANT=stat_host_bound is not set"""
-    return device_tables_enabled() and not _variant_listed("stat_host_bound")
 
 
 class _PendingBound(object):
@@ -779,11 +790,6 @@ EDGE_VARIANT_STATS = {"calls": 0, "edges": 0, "kernel_ms": 0.0, "lazy_expansions
 EDGE_VARIANT_BATCH = 4096
 
 
-def edge_variants_on_device_enabled():
-    """the variants of a round's edges come from the device: the device tables are on and ISOCON_DEBUG_VARIANT=stat_host_variants is not set"""
-    return device_tables_enabled() and not _variant_listed("stat_host_variants")
-
-
 class _LazyAlignments(object):
     """of_edge for a round whose alignments are ops: e -> ((aln_t, aln_c), (aln_c, aln_t)) of the (t, c) and the (c, t) alignment, expanded
     when asked for (EDGE_VARIANT_STATS["lazy_expansions"] counts the edges)"""
@@ -807,7 +813,7 @@ class _LazyAlignments(object):
 
 
 def _file_variant_records(rows):
-    """(variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c) from an edge's variant records in column order, each
+    """_EdgeVariants (variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c) from an edge's variant records in column order, each
     (i, key on t, key on c, u_v, type, p_t, p_c, snippet of aln_c, snippet of aln_t): filing every record under its keys in that order is
     the reference's loop (functions.get_variant_coordinates) -- a later variant on the same key overwrites the entry and keeps the key's place"""
     variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c = [], {}, {}, {}, {}
@@ -818,7 +824,7 @@ def _file_variant_records(rows):
         variant_coords_c[key_c] = entry
         alignment_c_to_t[key_t] = snip_c
         alignment_t_to_c[key_c] = snip_t
-    return variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c
+    return _EdgeVariants(variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c)
 
 
 def _edge_variant_capacities(ops, ops_ptr):
@@ -875,7 +881,7 @@ def _edge_variants_call(seqs, edge_t, edge_c, ops, ops_ptr, rec_ptr=None):
 
 
 def _tuples_from_edge_records(n, n_var, recs, snip_ptr, snip_c, snip_t, rec_ptr):
-    """the tuple of _edge_variants for every edge of an isocon_edge_variants answer"""
+    """the _EdgeVariants of _edge_variants for every edge of an isocon_edge_variants answer"""
     R = recs.tolist()
     sp = snip_ptr.tolist()
     first = (rec_ptr - rec_ptr[0]).tolist() if n else [0]
@@ -916,35 +922,31 @@ def _edge_variants_on_device(live, C, ops, ops_ptr):
 
 
 def _edge_variants(t_seq, c_seq, alignment_tc, alignment_ct):
-    """(variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c) of an edge from its two alignments"""
+    """_EdgeVariants (variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c) of an edge from its two alignments"""
     aln_t, aln_c, variants = _candidate_vs_reference(alignment_tc, alignment_ct)
-    return (variants,) + tuple(functions.get_variant_coordinates(t_seq, c_seq, aln_t, aln_c, variants))
+    return _EdgeVariants(variants, *functions.get_variant_coordinates(t_seq, c_seq, aln_t, aln_c, variants))
 
 
 def _test_on_tables(t_seq, c_seq, alignment_tc, alignment_ct, tab_c, tab_t, ccs_dict=None, max_phred_q_trusted=None):
     """_test_on_alignments on the read tables of c and t: same tuple, the supporting reads as a count."""
-    variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c = _edge_variants(t_seq, c_seq, alignment_tc, alignment_ct)
-    sup_c = np.flatnonzero(tab_c.agree_with_candidate(variant_coords_c))
-    sup_t = np.flatnonzero(tab_t.show_snippets(variant_coords_t, alignment_c_to_t))
-    return _test_on_supporters(t_seq, variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c, tab_c, tab_t, sup_c, sup_t,
-                               ccs_dict, max_phred_q_trusted)
+    ev = _edge_variants(t_seq, c_seq, alignment_tc, alignment_ct)
+    work_c = _SideWork(tab_c, np.flatnonzero(tab_c.agree_with_candidate(ev.coords_c)))
+    work_t = _SideWork(tab_t, np.flatnonzero(tab_t.show_snippets(ev.coords_t, ev.c_to_t)))
+    return _test_on_supporters(t_seq, ev, work_c, work_t, ccs_dict, max_phred_q_trusted)
 
 
-def _test_on_supporters(t_seq, variants, variant_coords_t, variant_coords_c, alignment_c_to_t, alignment_t_to_c, tab_c, tab_t, sup_c, sup_t,
-                        ccs_dict=None, max_phred_q_trusted=None, codes_c=None, codes_t=None, probs_c=None, probs_t=None, pending=None):
-    """The test of an edge once the supporting reads are known (sup_c / sup_t: ascending row indices into the tables of c / t, host
-    or device tables alike): error probabilities per read and the bound.  With base qualities, device tables bring probs_c / probs_t
-    (isocon_readtab_probability: one double per read, negative = not informative) or codes_c / codes_t (isocon_readtab_quality:
-    variants x reads); host tables compute theirs.  pending: the round's collector of _raghavan_on_arrays."""
+def _test_on_supporters(t_seq, ev, work_c, work_t, ccs_dict=None, max_phred_q_trusted=None, pending=None):
+    """The test of the edge ev (_EdgeVariants) once the supporting reads are known: error probabilities per read and the bound.  work_c / work_t
+    (_SideWork): the tables of c / t, host or device alike, their supporting rows and a device table's answer about qualities.  pending: the round's collector."""
+    variant_coords_t, tab_c, tab_t, sup_c, sup_t = ev.coords_t, work_c.tab, work_t.tab, work_c.supporters, work_t.supporters
     n_support = len(sup_c) + len(sup_t)
-    if len(variants) == 0:
+    if len(ev.variants) == 0:
         return variant_coords_t, 0.0, n_support, tab_c.n + tab_t.n
     if ccs_dict:
         # base qualities (functions.get_read_ccs_probabilities_c / _t): c's informative reads first, then t's
-        ratios = _error_ratios(tab_c, tab_t) if probs_c is None or probs_t is None else None          # (the device had them with its queries)
-        alive_c, prob_c = _ccs_probabilities_on_table(tab_c, variant_coords_c, alignment_t_to_c, ccs_dict, ratios, max_phred_q_trusted, "D", {"I": 0}, codes_c, probs_c)
-        alive_t, prob_t = _ccs_probabilities_on_table(tab_t, variant_coords_t, alignment_c_to_t, ccs_dict, ratios, max_phred_q_trusted, "I", {"D": 0, "I": -2},
-                                                      codes_t, probs_t)
+        ratios = None if work_c.probs is not None and work_t.probs is not None else _error_ratios(tab_c, tab_t)          # (the device had them with its queries)
+        alive_c, prob_c = _ccs_probabilities_on_table(_SIDE_C, work_c, ev, ccs_dict, ratios, max_phred_q_trusted)
+        alive_t, prob_t = _ccs_probabilities_on_table(_SIDE_T, work_t, ev, ccs_dict, ratios, max_phred_q_trusted)
         prob = np.concatenate([prob_c[alive_c], prob_t[alive_t]])
         if len(prob) == 0:
             assert n_support == 0
@@ -1025,13 +1027,10 @@ def do_statistical_tests_per_edge(nearest_neighbor_graph, C, X, read_partition, 
     every edge c -> t of the graph (nr_cores is irrelevant here: one device batch for all edges)."""
     edges = [(c_acc, t_acc) for c_acc in nearest_neighbor_graph for t_acc in nearest_neighbor_graph[c_acc]]
     live = [(c, t) for c, t in edges if len(read_partition[c]) + len(read_partition[t]) > 0]
-    pairs = []
-    for c, t in live:
-        pairs.append((C[t], C[c]))
-        pairs.append((C[c], C[t]))
+    pairs = [pair for c, t in live for pair in ((C[t], C[c]), (C[c], C[t]))]
     p_values = {c_acc: {} for c_acc in nearest_neighbor_graph}
-    on_device = device_tables_enabled()
-    if on_device and pairs and edge_variants_on_device_enabled():
+    routes = _routes()
+    if pairs and routes.variants:
         # the alignments stay ops: variants, coordinates and snippets of all edges from the device, gapped strings only on demand
         ops, ops_ptr = SWM._align_pairs(pairs, [-3] * len(pairs), 2, 3, 1, want_ops=True)
         of_edge = _LazyAlignments(live, C, ops, ops_ptr)
@@ -1040,8 +1039,8 @@ def do_statistical_tests_per_edge(nearest_neighbor_graph, C, X, read_partition, 
         alignments = SWM._align_pairs(pairs, [-3] * len(pairs), 2, 3, 1) if pairs else []
         of_edge = {e: (alignments[2 * i], alignments[2 * i + 1]) for i, e in enumerate(live)}
         variants_of = None
-    if on_device:
-        done = _tests_on_device(live, of_edge, C, read_partition, ccs_dict, getattr(params, "max_phred_q_trusted", None), variants_of)
+    if routes.tables:
+        done = _tests_on_device(live, of_edge, C, read_partition, ccs_dict, getattr(params, "max_phred_q_trusted", None), variants_of, routes)
     else:
         tables = _tables_for([(C[acc], read_partition[acc]) for e in live for acc in e])
     for c_acc, t_acc in edges:
@@ -1052,7 +1051,7 @@ def do_statistical_tests_per_edge(nearest_neighbor_graph, C, X, read_partition, 
         if ccs_dict:
             for x_acc in read_partition[c_acc]:
                 assert X[x_acc] == ccs_dict[x_acc].seq
-        if on_device:
+        if routes.tables:
             delta_t, p_value, n_support, used = done[(c_acc, t_acc)]
         else:
             tc, ct = of_edge[(c_acc, t_acc)]

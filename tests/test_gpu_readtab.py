@@ -81,7 +81,7 @@ def test_random_trials_equal_the_per_read_functions():
         got = dict(zip(accs_t + accs_c, np.stack([np.concatenate([tab_t.ins, tab_c.ins]), np.concatenate([tab_t.dele, tab_c.dele]),
                                                   np.concatenate([tab_t.sub, tab_c.sub])], axis=1).tolist()))
         assert {a: list(v) for a, v in want.items()} == got, n
-        fast = H._test_on_supporters(t, ev[0], ev[1], ev[2], ev[3], ev[4], tab_c, tab_t, np.asarray(sup[2 * n], dtype=np.int64), np.asarray(sup[2 * n + 1], dtype=np.int64))
+        fast = H._test_on_supporters(t, ev, H._SideWork(tab_c, np.asarray(sup[2 * n], dtype=np.int64)), H._SideWork(tab_t, np.asarray(sup[2 * n + 1], dtype=np.int64)))
         host = H._test_on_tables(t, c, tc, ct, H._ReadTable(len(c), reads_c), H._ReadTable(len(t), reads_t))
         assert list(host[0].items()) == list(fast[0].items()) and host[1:] == fast[1:], (n, host[1:], fast[1:])
         tested += host[1] not in (0.0, 1.0)

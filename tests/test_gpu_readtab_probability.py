@@ -112,13 +112,13 @@ def test_directed_shapes():
             coords, snippets = queries[qc][2], queries[qc][3]
             sup_c, sup_t = H._device_support(tab.set.handle, [(k0, 0, coords, None, tab.n), (k0, 1, coords, snippets, tab.n)])
             results = []
-            for kw in (dict(codes_c=codes[qc], codes_t=codes[qt]), dict(probs_c=got[qc][0], probs_t=got[qt][0])):
-                args = ("ACGT", [("variant",)], coords, coords, snippets, snippets, tab, tab, sup_c, sup_t, ccs, 43)
+            for work_c, work_t in ((H._SideWork(tab, sup_c, codes[qc]), H._SideWork(tab, sup_t, codes[qt])), (H._SideWork(tab, sup_c, probs=got[qc][0]), H._SideWork(tab, sup_t, probs=got[qt][0]))):
+                args = ("ACGT", H._EdgeVariants([("variant",)], coords, coords, snippets, snippets), work_c, work_t, ccs, 43)
                 if raises:
                     with pytest.raises(AssertionError):
-                        H._test_on_supporters(*args, **kw)
+                        H._test_on_supporters(*args)
                 else:
-                    results.append(H._test_on_supporters(*args, **kw))
+                    results.append(H._test_on_supporters(*args))
             assert raises or (results[0] == results[1] and results[0][2:] == (2, 4))
     # dropped at the second variant, both sequences shown at the third
     q0, _ = marks["dropped"]
@@ -173,8 +173,8 @@ def test_status_and_what_the_route_raises(case, monkeypatch):
     calls = []
     if raises is None:
         host_c, host_t = H._ReadTable(*items[0]), H._ReadTable(*items[1])
-        host = H._test_on_supporters(C["t"], [("variant",)], vt, vc, ac2t, at2c, host_c, host_t, np.flatnonzero(host_c.agree_with_candidate(vc)),
-                                     np.flatnonzero(host_t.show_snippets(vt, ac2t)), ccs, 43)
+        host = H._test_on_supporters(C["t"], H._EdgeVariants([("variant",)], vt, vc, ac2t, at2c), H._SideWork(host_c, np.flatnonzero(host_c.agree_with_candidate(vc))),
+                                     H._SideWork(host_t, np.flatnonzero(host_t.show_snippets(vt, ac2t))), ccs, 43)
         assert route(None)[0][("c", "t")] == host and route("stat_host_prob")[0][("c", "t")] == host
     else:
         for variant in (None, "stat_host_prob"):

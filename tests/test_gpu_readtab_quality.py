@@ -67,8 +67,9 @@ def test_reference_fixture():
             tab_c, tab_t = tabs[2 * n], tabs[2 * n + 1]
             sums = [float(max(1.0, int(getattr(tab_t, e).sum() + getattr(tab_c, e).sum()))) for e in ("sub", "ins", "dele")]
             ratios = tuple(x / sum(sums) for x in sums)
-            for tab, coords, snippets, code, want, shifted, other in ((tab_c, vc, at2c, codes[2 * n], want_c, "D", {"I": 0}), (tab_t, vt, ac2t, codes[2 * n + 1], want_t, "I", {"D": 0, "I": -2})):
-                alive, prob = H._ccs_probabilities_on_table(tab, coords, snippets, ccs, ratios, 43, shifted, other, code)
+            ev = H._EdgeVariants([("variant",)], vt, vc, ac2t, at2c)
+            for side, tab, code, want in ((H._SIDE_C, tab_c, codes[2 * n], want_c), (H._SIDE_T, tab_t, codes[2 * n + 1], want_t)):
+                alive, prob = H._ccs_probabilities_on_table(side, H._SideWork(tab, codes=code), ev, ccs, ratios, 43)
                 assert [[a, repr(float(p))] for a, p, ok in zip(tab.accs, prob, alive) if ok] == want[0], n
                 assert sorted(a for a, ok in zip(tab.accs, alive) if not ok) == sorted(want[1]), n
                 n_prob += len(want[0])
@@ -147,17 +148,18 @@ def test_error_codes_raise_only_on_informative_reads(case):
     items = [(len(next(iter(rc.values()))[0].replace("-", "")) if rc else 4, rc), (len(next(iter(rt.values()))[0].replace("-", "")) if rt else 4, rt)]
     queries = [(0, 0, vc, at2c), (1, 1, vt, ac2t)]
     host_c, host_t = H._ReadTable(items[0][0], rc), H._ReadTable(items[1][0], rt)
+    ev = H._EdgeVariants([("variant",)], vt, vc, ac2t, at2c)
     sup_c, sup_t = np.flatnonzero(host_c.agree_with_candidate(vc)), np.flatnonzero(host_t.show_snippets(vt, ac2t))
 
     def on_host():
-        return H._test_on_supporters("ACGT", [("variant",)], vt, vc, ac2t, at2c, host_c, host_t, sup_c, sup_t, ccs, 43)
+        return H._test_on_supporters("ACGT", ev, H._SideWork(host_c, sup_c), H._SideWork(host_t, sup_t), ccs, 43)
 
     with device_set(items, ccs) as tabs:
         dsup = H._device_support(tabs[0].set.handle, RC.with_rows(items, [(0, 0, vc, None), (1, 1, vt, ac2t)]))
         codes = H._device_quality(tabs[0].set.handle, QC.with_rows(items, queries))
 
         def on_device():
-            return H._test_on_supporters("ACGT", [("variant",)], vt, vc, ac2t, at2c, tabs[0], tabs[1], dsup[0], dsup[1], ccs, 43, codes[0], codes[1])
+            return H._test_on_supporters("ACGT", ev, H._SideWork(tabs[0], dsup[0], codes[0]), H._SideWork(tabs[1], dsup[1], codes[1]), ccs, 43)
 
         if raises is None:
             assert {QC.Q_INDEX, QC.Q_BEYOND, QC.Q_BOTH} & set(np.concatenate([c.ravel() for c in codes]).tolist())          # (the error code is there)
