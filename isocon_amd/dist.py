@@ -16,6 +16,10 @@ phase 2 = 128/256/512-row bands and the un-banded kernel, only if the reduced bo
     all_gather of the candidate edges that attain best[] on their rank, in fixed-size blocks of the largest count
     known from the last reduction (no size exchange)                                           (12 B x edges)
 The reference has no distributed path (its Pool chunking: /root/reference/modules/nearest_neighbor_graph.py:33-35).
+
+Explicit pair lists (sharded_ed_pairs, _hw_pairs, _sg_trace, _path_pairs) are dealt round-robin by size.  The hypothesis tests of a round
+are dealt by EDGE (shard_edges: contiguous runs of the canonical edge list, balanced by reads); their rows travel as Python objects, the
+protocol is hypothesis_test_module._shared_rows.
 """
 from __future__ import annotations
 
@@ -536,3 +540,40 @@ def sharded_path_pairs(store, q, t, k=None, infix=False, dist=None, device=None)
             out_ops[out_ptr[p]:out_ptr[p + 1]] = o[src_ptr[i]:src_ptr[i + 1]]
             out_head[p] = hh[i]
     return (out_head if infix else out_head.reshape(-1)), out_ops, out_ptr.astype(np.uint64)
+
+
+# ---- the hypothesis tests of a round (hypothesis_test_module.do_statistical_tests_per_edge): one owner per edge -----------
+def canonical_edges(edge_keys):
+    """positions of the edges (c_acc, t_acc) in canonical order: by the two accessions as strings -- the same on every rank, whatever
+    order the rank's dicts (they go back to Python sets, and PYTHONHASHSEED differs between the processes) list them in"""
+    return sorted(range(len(edge_keys)), key=lambda i: (str(edge_keys[i][0]), str(edge_keys[i][1])))
+
+
+def shard_edges(edge_keys, weights, world):
+    """Owner of every edge of a round: [the edges of rank 0, of rank 1, ...], each run in canonical order (canonical_edges).  A pure
+    function of its arguments -- the order in which the edges come in does not matter.  weights[i] (a positive integer: 1 + the reads of
+    the edge's two candidates) is what edge i costs.  The canonical list is cut into `world` CONTIGUOUS runs: an edge belongs to the rank
+    in whose 1 / world of the summed weight its midpoint falls, so a run carries at most total / world + max(weight) (half an edge can
+    stick out at either end).  Contiguity keeps the edges of one c on one rank, c's read table is built once; the table of a t that
+    many candidates point to may be built on several ranks."""
+    world = max(int(world), 1)
+    order = canonical_edges(edge_keys)
+    runs = [[] for _ in range(world)]
+    total = sum(int(weights[i]) for i in order)
+    before = 0
+    for i in order:
+        w = int(weights[i])
+        if w <= 0:
+            raise ValueError("shard_edges: weights are positive integers")
+        runs[min(world - 1, (2 * before + w) * world // (2 * total))].append(edge_keys[i])
+        before += w
+    return runs
+
+
+def edge_digest(edge_keys, weights):
+    """63-bit digest of a round's edges and weights in canonical order (hashlib: the same in every process), for same_everywhere"""
+    import hashlib
+    h = hashlib.blake2b(digest_size=8)
+    for i in canonical_edges(edge_keys):
+        h.update(("%s\0%s\0%d\n" % (edge_keys[i][0], edge_keys[i][1], int(weights[i]))).encode("utf-8"))
+    return int.from_bytes(h.digest(), "little") >> 1

@@ -655,17 +655,20 @@ class _SideWork(object):
         self.status = self.support_query = self.quality_query = self.ratios = None
 
 
-def _tests_on_device(live, of_edge, C, read_partition, ccs_dict=None, max_phred_q_trusted=None, variants_of=None, routes=None):
+def _tests_on_device(live, of_edge, C, read_partition, ccs_dict=None, max_phred_q_trusted=None, variants_of=None, routes=None, at=None):
     """{edge: (variant_coords_t, p_value, supporting reads, reads used)} for the edges of a round: supporters and error counts from the device tables, one
     support call per table set; with base qualities (ccs_dict) also every read's probability (or, under ISOCON_DEBUG_VARIANT=stat_host_prob, its quality
     code at every variant for the host to multiply up), one call per table set. An edge for which the device reports that something is to be raised goes
     through the codes, where it is raised. An edge with a variant coordinate that the per-read statement cannot index stays on the host tables, where it
     raises; so does an edge of a table set whose qualities cannot be attached. variants_of: {edge: its _edge_variants} where the caller has them
     (_edge_variants_on_device); of_edge[e], the two gapped alignments, is then looked at only for the edges that stay on the host tables
-    (_LazyAlignments). The bounds of these edges follow in one call after their loop (_resolve_bounds) if routes, the round's _routes(), says so."""
+    (_LazyAlignments). The bounds of these edges follow in one call after their loop (_resolve_bounds) if routes, the round's _routes(), says so.
+    at: a one-element list that names the edge at work (None during a call for a whole batch), for a caller that has to know whose test raised."""
     routes = _routes() if routes is None else routes
+    at = [None] if at is None else at
     prepared, on_host = {}, []
     for e in live:
+        at[0] = e
         c_acc, t_acc = e
         ev = variants_of[e] if variants_of is not None else _edge_variants(C[t_acc], C[c_acc], of_edge[e][0], of_edge[e][1])
         ev = ev if type(ev) is _EdgeVariants else _EdgeVariants._make(ev)          # (a plain tuple from a caller of its own)
@@ -673,10 +676,12 @@ def _tests_on_device(live, of_edge, C, read_partition, ccs_dict=None, max_phred_
             prepared[e] = ev
         else:
             on_host.append(e)
+    at[0] = None
     tables = _tables_for([(C[acc], read_partition[acc]) for e in prepared for acc in e], _DEVICE_TABLES, _build_device_tables)
     on_device_prob = bool(ccs_dict) and routes.probabilities
     work, by_set = {}, {}          # edge -> (its variants, its c side, its t side); id(table set) -> the sides on it, in edge order
     for e, ev in prepared.items():
+        at[0] = e
         sides = [_SideWork(tables[id(read_partition[acc])]) for acc in e]
         if ccs_dict and not all(item.tab.set.attach_qualities(ccs_dict) for item in sides):
             on_host.append(e)
@@ -690,6 +695,7 @@ def _tests_on_device(live, of_edge, C, read_partition, ccs_dict=None, max_phred_
             if with_qualities:
                 item.quality_query, item.ratios = _Query(tab.k, side.kind, coords, side.quality_snippets(ev), tab.n), ratios
             by_set.setdefault(id(item.tab.set), []).append(item)
+    at[0] = None
     for batch in by_set.values():
         handle = batch[0].tab.set.handle
         for item, sup in zip(batch, _device_support(handle, [item.support_query for item in batch])):
@@ -707,18 +713,22 @@ def _tests_on_device(live, of_edge, C, read_partition, ccs_dict=None, max_phred_
     pending = [] if routes.bounds else None          # (m_sum, y_sum) of the tests whose bound is still to come: the p-values are then _PendingBound
     try:
         for e, (ev, work_c, work_t) in work.items():          # (in edge order)
+            at[0] = e
             if work_c.status or work_t.status:
                 # something is to be raised on this edge: its code bytes, and the host's loop over them raises it (c's reads before t's)
                 for item in (work_c, work_t):
                     item.codes, item.probs = _device_quality(item.tab.set.handle, [item.quality_query])[0], None
             results[e] = _test_on_supporters(C[e[1]], ev, work_c, work_t, ccs_dict, max_phred_q_trusted, pending)
     except (Exception, SystemExit):          # (what the tests themselves raise -- SystemExit is one of them --, not an interrupt)
-        _resolve_bounds(results, pending)          # the bound of an earlier edge that is to raise raises first, as it did
+        raised_at = at[0]
+        _resolve_bounds(results, pending, at)          # the bound of an earlier edge that is to raise raises first, as it did
+        at[0] = raised_at
         raise
-    _resolve_bounds(results, pending)
+    _resolve_bounds(results, pending, at)
     if on_host:
         host = _tables_for([(C[acc], read_partition[acc]) for e in on_host for acc in e])
         for e in on_host:
+            at[0] = e
             results[e] = _test_on_tables(C[e[1]], C[e[0]], of_edge[e][0], of_edge[e][1], host[id(read_partition[e[0]])], host[id(read_partition[e[1]])],
                                          ccs_dict, max_phred_q_trusted)
     return results
@@ -760,11 +770,13 @@ def _device_bounds(m_sums, y_sums):
     return bounds[:n], certified
 
 
-def _resolve_bounds(results, pending):
+def _resolve_bounds(results, pending, at=None):
     """the _PendingBound of every test in `results` replaced by its p-value: one _device_bounds call for the collector (several only above
-    BOUND_CALL_BYTES), then _raghavan_from_sums for the tests that came back without a certificate, in the order of `results`"""
+    BOUND_CALL_BYTES), then _raghavan_from_sums for the tests that came back without a certificate, in the order of `results`.  at: as in _tests_on_device"""
     if not pending:
         return
+    at = [None] if at is None else at
+    at[0] = None
     per_call = max(1, BOUND_CALL_BYTES // 25)          # (16 bytes up, 9 bytes down per test)
     bounds, certified = [], []
     for lo in range(0, len(pending), per_call):
@@ -778,6 +790,7 @@ def _resolve_bounds(results, pending):
                 p_value = bounds[p_value.at]
             else:
                 BOUND_STATS["host_fallbacks"] += 1
+                at[0] = e
                 p_value = _raghavan_from_sums(*pending[p_value.at])
             results[e] = (variant_coords_t, p_value, n_support, used)
     del pending[:]
@@ -1022,14 +1035,13 @@ def statistical_test(c_acc, t_acc, c_seq, t_seq, reads_to_c, read_alignments_to_
     return _result(c_acc, t_acc, t_seq, delta_t, p_value, reads_support, used, bool(ccs_dict))
 
 
-def do_statistical_tests_per_edge(nearest_neighbor_graph, C, X, read_partition, ccs_dict, params):
-    """hypothesis_test_module.py:20-77: {c_acc: {t_acc: (p_value, correction factor, support, reads used, variants)}} for
-    every edge c -> t of the graph (nr_cores is irrelevant here: one device batch for all edges)."""
-    edges = [(c_acc, t_acc) for c_acc in nearest_neighbor_graph for t_acc in nearest_neighbor_graph[c_acc]]
-    live = [(c, t) for c, t in edges if len(read_partition[c]) + len(read_partition[t]) > 0]
+def _tests_of(live, C, read_partition, ccs_dict, params, routes, at=None):
+    """The tests of the edges `live` (each with reads on c or on t), in that order: the alignments of their candidates in one batch, their
+    variants in one device call, the tests on the device tables -- or, where routes says so, on the host tables.  Returns (of_edge, test):
+    `e in of_edge` iff e is one of `live`; test(e) = (variant_coords_t, p_value, supporting reads, reads used), already there on the device
+    route, evaluated when asked on the host tables.  at: see _tests_on_device."""
+    max_q = getattr(params, "max_phred_q_trusted", None)
     pairs = [pair for c, t in live for pair in ((C[t], C[c]), (C[c], C[t]))]
-    p_values = {c_acc: {} for c_acc in nearest_neighbor_graph}
-    routes = _routes()
     if pairs and routes.variants:
         # the alignments stay ops: variants, coordinates and snippets of all edges from the device, gapped strings only on demand
         ops, ops_ptr = SWM._align_pairs(pairs, [-3] * len(pairs), 2, 3, 1, want_ops=True)
@@ -1040,9 +1052,96 @@ def do_statistical_tests_per_edge(nearest_neighbor_graph, C, X, read_partition, 
         of_edge = {e: (alignments[2 * i], alignments[2 * i + 1]) for i, e in enumerate(live)}
         variants_of = None
     if routes.tables:
-        done = _tests_on_device(live, of_edge, C, read_partition, ccs_dict, getattr(params, "max_phred_q_trusted", None), variants_of, routes)
+        return of_edge, _tests_on_device(live, of_edge, C, read_partition, ccs_dict, max_q, variants_of, routes, at).__getitem__
+    tables = _tables_for([(C[acc], read_partition[acc]) for e in live for acc in e])
+
+    def on_host_tables(e):
+        tc, ct = of_edge[e]
+        return _test_on_tables(C[e[1]], C[e[0]], tc, ct, tables[id(read_partition[e[0]])], tables[id(read_partition[e[1]])], ccs_dict, max_q)
+
+    return of_edge, on_host_tables
+
+
+# ---- one process per GPU: a round's edges shared between the ranks (dist.shard_edges) ----
+# rounds: the sharded rounds of this process; edges_owned / edges_total: the live edges this rank tested itself / all live edges of those
+# rounds; gather_bytes: the pickled rows (and exception) this rank put into the rounds' all_gather_object
+SHARD_STATS = {"rounds": 0, "edges_owned": 0, "edges_total": 0, "gather_bytes": 0}
+
+
+def _sharing_group():
+    """torch.distributed when a round's edges are shared between the ranks: the caller runs one process per GPU (world size above 1) and
+    ISOCON_DEBUG_VARIANT=stat_all_edges -- every rank tests all edges itself -- is not set"""
+    from .nearest_neighbor_graph import _process_group
+    listed = {item.split("=")[0] for item in os.environ.get("ISOCON_DEBUG_VARIANT", "").split(",")}
+    return None if "stat_all_edges" in listed else _process_group()
+
+
+def _travels(exc):
+    """exc if it survives pickling (all_gather_object), else a RuntimeError that quotes it"""
+    import pickle
+    try:
+        pickle.loads(pickle.dumps(exc))
+        return exc
+    except Exception:          # noqa: BLE001
+        return RuntimeError("do_statistical_tests_per_edge: %r" % (exc,))
+
+
+def _shared_rows(group, edges, live, C, read_partition, ccs_dict, params, routes):
+    """{edge: _result(...)[2:]} for all edges of `live`, each tested by ONE rank of the group: the edges are dealt by dist.shard_edges (weight 1
+    + the reads of c and of t), a rank runs _tests_of and _result for its own edges in its own order, one all_gather_object brings every rank's
+    rows (doubles travel exactly) to every rank.  Collectives per round: one reduction that confirms that the ranks hold the same edges and
+    weights (a RuntimeError on every rank otherwise), and the gather.  A rank whose share raises -- SystemExit and AssertionError are among
+    what a test raises -- stops there, sends the exception with its edge in place of the remaining rows, and every rank raises, of the gathered
+    exceptions, the one whose edge comes first in `edges`, its own order.  (With ONE raising edge that is what a single process raises.  With
+    several it need not be: a single process goes through its edges in phases -- all tests on the device tables before the edges left to the
+    host tables --, so there an edge whose device answer raises comes before an earlier edge that raises on the host tables.)"""
+    import pickle
+    from . import dist as D
+    weights = [1 + len(read_partition[c]) + len(read_partition[t]) for c, t in live]
+    if not D.same_everywhere(D.edge_digest(live, weights), group):
+        raise RuntimeError("do_statistical_tests_per_edge: the ranks hold different edges / read partitions (digest mismatch); "
+                           "every rank must run the same round on the same input")
+    world, rank = group.get_world_size(), group.get_rank()
+    mine = set(D.shard_edges(live, weights, world)[rank])
+    own = [e for e in live if e in mine]
+    rows, failed, at = {}, None, [None]
+    try:
+        if own:          # (a rank without an edge makes no device call)
+            _, test = _tests_of(own, C, read_partition, ccs_dict, params, routes, at)
+            for e in own:
+                at[0] = e
+                delta_t, p_value, n_support, used = test(e)
+                rows[e] = _result(e[0], e[1], C[e[1]], delta_t, p_value, range(n_support), used, bool(ccs_dict))[2:]
+    except (Exception, SystemExit) as exc:          # (what the tests themselves raise, not an interrupt); a failure of a whole batch counts for its first edge
+        failed = (own[0] if at[0] is None else at[0], _travels(exc))
+    SHARD_STATS["rounds"] += 1
+    SHARD_STATS["edges_owned"] += len(own)
+    SHARD_STATS["edges_total"] += len(live)
+    sent = pickle.dumps((rows, failed), pickle.HIGHEST_PROTOCOL)          # pickled HERE, once: the gather then only copies the bytes, and their number is known
+    SHARD_STATS["gather_bytes"] += len(sent)
+    gathered = [None] * world
+    group.all_gather_object(gathered, sent)
+    gathered = [pickle.loads(part) for part in gathered]
+    failures = [f for _, f in gathered if f is not None]
+    if failures:
+        place = {e: k for k, e in enumerate(edges)}
+        raise min(failures, key=lambda f: place[f[0]])[1]
+    return {e: row for part, _ in gathered for e, row in part.items()}
+
+
+def do_statistical_tests_per_edge(nearest_neighbor_graph, C, X, read_partition, ccs_dict, params):
+    """hypothesis_test_module.py:20-77: {c_acc: {t_acc: (p_value, correction factor, support, reads used, variants)}} for
+    every edge c -> t of the graph (nr_cores is irrelevant here: one device batch for all edges; one process per GPU: one batch
+    per rank for its share of the edges, _shared_rows)."""
+    edges = [(c_acc, t_acc) for c_acc in nearest_neighbor_graph for t_acc in nearest_neighbor_graph[c_acc]]
+    live = [(c, t) for c, t in edges if len(read_partition[c]) + len(read_partition[t]) > 0]
+    p_values = {c_acc: {} for c_acc in nearest_neighbor_graph}
+    routes = _routes()
+    group = _sharing_group()
+    if group is None:
+        of_edge, test = _tests_of(live, C, read_partition, ccs_dict, params, routes)
     else:
-        tables = _tables_for([(C[acc], read_partition[acc]) for e in live for acc in e])
+        of_edge = _shared_rows(group, edges, live, C, read_partition, ccs_dict, params, routes)
     for c_acc, t_acc in edges:
         if (c_acc, t_acc) not in of_edge:
             p_values[c_acc][t_acc] = (1.0, 1.0, 0, 0, "")
@@ -1051,13 +1150,11 @@ def do_statistical_tests_per_edge(nearest_neighbor_graph, C, X, read_partition, 
         if ccs_dict:
             for x_acc in read_partition[c_acc]:
                 assert X[x_acc] == ccs_dict[x_acc].seq
-        if routes.tables:
-            delta_t, p_value, n_support, used = done[(c_acc, t_acc)]
+        if group is None:
+            delta_t, p_value, n_support, used = test((c_acc, t_acc))
+            p_values[c_acc][t_acc] = _result(c_acc, t_acc, C[t_acc], delta_t, p_value, range(n_support), used, bool(ccs_dict))[2:]
         else:
-            tc, ct = of_edge[(c_acc, t_acc)]
-            delta_t, p_value, n_support, used = _test_on_tables(C[t_acc], C[c_acc], tc, ct, tables[id(read_partition[c_acc])],
-                                                                tables[id(read_partition[t_acc])], ccs_dict, getattr(params, "max_phred_q_trusted", None))
-        p_values[c_acc][t_acc] = _result(c_acc, t_acc, C[t_acc], delta_t, p_value, range(n_support), used, bool(ccs_dict))[2:]
+            p_values[c_acc][t_acc] = of_edge[(c_acc, t_acc)]
     return p_values
 
 
