@@ -122,6 +122,31 @@ int isocon_qgram_bound_pairs(isocon_store *s, const uint32_t *a, const uint32_t 
 int isocon_block_bound_pairs(isocon_store *s, const uint32_t *owner, const uint32_t *partner, uint64_t n_pairs, int32_t probe_stride, int32_t *out_count);
 
 /*
+ * The two kernels of the main pass that APPLY that bound (csrc/nn_filter.hpp: k_nn_block_filter, k_nn_block_filter2), run on chunks the
+ * caller made (tests): the launches, grids and buffer layout are the main pass's own.  The reference has no counterpart.
+ *   thr[i], i < store size     threshold of entry i, 0 .. 64 (the 7-bit field of the main pass's per-entry word)
+ *   chunk c < n_chunks         owner[c], narrow[c] (0: 64-row class, 1: 32-row class), list words words[chunk_ptr[c] .. chunk_ptr[c + 1]):
+ *                              1 .. 2111 of them (what the list builder hands over: its chunk size + 63); chunk_ptr[0] = 0.  A list word is
+ *                              partner | bit 30 (the owner's threshold applies) | bit 31 (the partner's applies); the pair's threshold is
+ *                              min(kcap, the larger of those that apply), -1 with neither bit.
+ *   kcap, list_min (>= 1), second_pass (0 / 1)
+ * A pair survives the first pass iff count(owner, partner, stride 4) <= its threshold.  With np survivors of a chunk of `count` pairs:
+ * np >= list_min and (no second pass or 2 np >= count): they stay a chunk of the chunk's class; else, with the second pass and np >= 16,
+ * they pass it (64 per task; survivors: count(.., stride 2) <= threshold as well) to the flat pairs; else they join the flat pairs as they are.
+ * Out: the chunks left, the 64-row class first -- out_slot / out_count / out_begin[i], i < out_counters[0] + out_counters[1], their words at
+ * out_list[out_begin[i] ..) in no defined order (out_list: all chunk_ptr[n_chunks] words of the list after the passes); the flat pairs
+ * out_pa / out_pb[i], i < out_counters[2], in no defined order.  out_counters[9] = chunks left of the 64-row class, of the 32-row class, flat
+ * pairs, pairs rejected by the first pass, by the second, pairs in the chunks left, of those in 32-row chunks, tasks of the second pass, the
+ * kernels' overflow word (always 0: the device buffers hold the worst case).
+ * ISOCON_E_ARG: an index out of range, a chunk of 0 or more than 2111 words, thr outside 0 .. 64, chunks_cap < n_chunks, list_cap or
+ * pairs_cap < chunk_ptr[n_chunks] (every pair kept), sequences of 16384 bases or more.  Same alphabet rule as isocon_qgram_bound_pairs.
+ */
+int isocon_block_filter_chunks(isocon_store *s, const int32_t *thr, uint32_t n_chunks, const uint32_t *owner, const uint8_t *narrow, const uint64_t *chunk_ptr,
+                               const uint32_t *words, int32_t kcap, uint32_t list_min, int32_t second_pass, uint32_t *out_slot, uint32_t *out_count,
+                               uint64_t *out_begin, uint64_t chunks_cap, uint32_t *out_list, uint64_t list_cap, uint32_t *out_pa, uint32_t *out_pb, uint64_t pairs_cap,
+                               uint64_t *out_counters);
+
+/*
  * The bound matrix the main pass of isocon_nn_graph / isocon_nn_partial consults for the shard (q_begin, q_end, q_stride, q_block) --
  * see isocon_nn_partial -- of a length-sorted store, read back for tests: row r belongs to the shard's r-th entry q, its bytes
  * out_bounds[out_row_ptr[r] .. out_row_ptr[r + 1]) are min(255, bound) of the pairs (q, p), p = q + 1, q + 2, ... while

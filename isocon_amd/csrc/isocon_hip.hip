@@ -1137,6 +1137,83 @@ extern "C" int isocon_block_bound_pairs(isocon_store *s, const uint32_t *owner, 
     return ISOCON_OK;
 }
 
+// ... and the two kernels of the main pass that apply it, on chunks the caller made (tests): the buffers are laid out as NNContext::plan_lists
+// lays them out and the launches are its own (nnf_launch_filter); every capacity holds the worst case, so the kernels never report an overflow
+extern "C" int isocon_block_filter_chunks(isocon_store *s, const int32_t *thr, uint32_t n_chunks, const uint32_t *owner, const uint8_t *narrow, const uint64_t *chunk_ptr,
+                                          const uint32_t *words, int32_t kcap, uint32_t list_min, int32_t second_pass, uint32_t *out_slot, uint32_t *out_count,
+                                          uint64_t *out_begin, uint64_t chunks_cap, uint32_t *out_list, uint64_t list_cap, uint32_t *out_pa, uint32_t *out_pb, uint64_t pairs_cap,
+                                          uint64_t *out_counters)
+{
+    if (!s || !out_counters || (second_pass != 0 && second_pass != 1) || list_min == 0) return ISOCON_E_ARG;
+    for (int i = 0; i < 9; ++i) out_counters[i] = 0;
+    if (!n_chunks) return ISOCON_OK;
+    if (!thr || !owner || !narrow || !chunk_ptr || !words || !out_slot || !out_count || !out_begin || !out_list || !out_pa || !out_pb) return ISOCON_E_ARG;
+    if (s->n_exc) { g_last_error = "block bounds are defined on the 2-bit planes: the set holds more than four distinct symbols"; return ISOCON_E_ALPHABET; }
+    const uint32_t n = s->dev.n;
+    if (n >= (1u << 30) || s->maxlen >= 16384) return ISOCON_E_ARG;          // (the list word's 30 index bits, the meta word's 14 length bits)
+    for (uint32_t i = 0; i < n; ++i)
+        if (thr[i] < 0 || thr[i] > 64) { g_last_error = "threshold outside 0 .. 64"; return ISOCON_E_ARG; }
+    // a chunk of the list builder holds 1 .. NN_LIST_CHUNK + 63 pairs: it leaves as soon as a group of 64 row positions has filled the buffer
+    // to NN_LIST_CHUNK (nn_surv_core.hpp), and the filter's pass[] holds NN_STAGE
+    static_assert(NN_LIST_CHUNK + 63 <= NN_STAGE, "a chunk fits the filter's staging buffer");
+    if (chunk_ptr[0] != 0) return ISOCON_E_ARG;
+    uint32_t n_narrow = 0;
+    for (uint32_t c = 0; c < n_chunks; ++c) {
+        if (owner[c] >= n || narrow[c] > 1) { g_last_error = "chunk owner out of range"; return ISOCON_E_ARG; }
+        if (chunk_ptr[c + 1] <= chunk_ptr[c] || chunk_ptr[c + 1] - chunk_ptr[c] > NN_LIST_CHUNK + 63) { g_last_error = "chunk count outside 1 .. NN_LIST_CHUNK + 63"; return ISOCON_E_ARG; }
+        n_narrow += narrow[c];
+    }
+    const uint64_t total = chunk_ptr[n_chunks];
+    for (uint64_t i = 0; i < total; ++i)
+        if ((words[i] & 0x3fffffffu) >= n) { g_last_error = "partner index out of range"; return ISOCON_E_ARG; }
+    if (chunks_cap < n_chunks || list_cap < total || pairs_cap < total) { g_last_error = "an output capacity below the worst case (every pair kept)"; return ISOCON_E_ARG; }
+    // meta words in the layout of k_nn_entry_meta (no roles, no score: the filter reads the threshold alone); chunk records, wide in front
+    const uint64_t cap_in = n_chunks, cap_out = n_chunks;
+    const uint64_t tasks_cap = second_pass ? 2 * cap_in + total / 64 + 1 : 0;
+    std::vector<uint32_t> meta((size_t)n + NN_META_PAD, 0u);
+    for (uint32_t i = 0; i < n; ++i) meta[i] = ((uint32_t)s->lens[i] & 0x3fffu) | ((uint32_t)thr[i] << 14);
+    std::vector<NNChunk> chunks(2 * (size_t)cap_in);
+    NNPlanTotals tot;
+    memset(&tot, 0, sizeof(tot));
+    for (uint32_t c = 0; c < n_chunks; ++c) {
+        NNChunk ch; ch.slot = owner[c]; ch.count = (uint32_t)(chunk_ptr[c + 1] - chunk_ptr[c]); ch.begin = chunk_ptr[c];
+        chunks[narrow[c] ? cap_in + tot.n_chunks_narrow++ : tot.n_chunks++] = ch;
+    }
+    const uint32_t stride = nnf_text2_stride(s->maxlen);
+    DevBuf d_text(&s->pool, SLOT_NN_TEXT2), d_meta(&s->pool, SLOT_NN_LDEST), d_tot(&s->pool, SLOT_NN_LTOT), d_chunks(&s->pool, SLOT_NN_LCHUNKS), d_list(&s->pool, SLOT_NN_LIST),
+        d_pa(&s->pool, SLOT_NN_LPA), d_pb(&s->pool, SLOT_NN_LPB), d_tasks(&s->pool, SLOT_NN_LTASKS);
+    int rc;
+    if ((rc = d_text.alloc((size_t)n * stride * 4)) || (rc = d_meta.alloc(meta.size() * 4)) || (rc = d_tot.alloc(sizeof(NNPlanTotals))) ||
+        (rc = d_chunks.alloc((size_t)(2 * cap_in + 2 * cap_out) * sizeof(NNChunk))) || (rc = d_list.alloc((size_t)total * 4)) || (rc = d_pa.alloc((size_t)total * 4)) ||
+        (rc = d_pb.alloc((size_t)total * 4)) || (rc = d_tasks.alloc((size_t)std::max<uint64_t>(tasks_cap, 1) * sizeof(NNFTask))))
+        return rc;
+    ISO_HIP_CHECK(copy_h2d(d_meta.p, meta.data(), meta.size() * 4));
+    ISO_HIP_CHECK(copy_h2d(d_tot.p, &tot, sizeof(tot)));
+    ISO_HIP_CHECK(copy_h2d(d_chunks.p, chunks.data(), chunks.size() * sizeof(NNChunk)));
+    ISO_HIP_CHECK(copy_h2d(d_list.p, words, (size_t)total * 4));
+    NNChunk *left = d_chunks.as<NNChunk>() + 2 * cap_in;
+    hipLaunchKernelGGL(k_build_text2, dim3(n), dim3(256), 0, 0, s->dev, d_text.as<uint32_t>(), stride);
+    ISO_HIP_CHECK(hipGetLastError());
+    ISO_HIP_CHECK(nnf_launch_filter(d_text.as<uint32_t>(), stride, s->dev.lens, d_meta.as<uint32_t>(), kcap, d_list.as<uint32_t>(), d_chunks.as<NNChunk>(), cap_in, left, cap_out,
+                                    d_pa.as<uint32_t>(), d_pb.as<uint32_t>(), total, d_tot.as<NNPlanTotals>(), list_min, second_pass ? d_tasks.as<NNFTask>() : (NNFTask *)nullptr,
+                                    tasks_cap));
+    ISO_HIP_CHECK(memcpy_wait(&tot, d_tot.p, sizeof(tot), hipMemcpyDeviceToHost));
+    const uint64_t counters[9] = {tot.f_chunks, tot.f_chunks_narrow, tot.n_small, tot.f_rejected, tot.f_rejected2, tot.f_listed, tot.f_narrow_listed, tot.f_tasks, tot.overflow};
+    for (int i = 0; i < 9; ++i) out_counters[i] = counters[i];
+    if (tot.overflow || tot.f_chunks > cap_in - n_narrow || tot.f_chunks_narrow > n_narrow || tot.n_small > total) { g_last_error = "the block filter left more than it was given"; return ISOCON_E_HIP; }
+    // the chunks left for the tables, wide then narrow; the list they index; the flat pairs
+    std::vector<NNChunk> out((size_t)(tot.f_chunks + tot.f_chunks_narrow));
+    if (tot.f_chunks) ISO_HIP_CHECK(copy_d2h(out.data(), left, (size_t)tot.f_chunks * sizeof(NNChunk)));
+    if (tot.f_chunks_narrow) ISO_HIP_CHECK(copy_d2h(out.data() + tot.f_chunks, left + cap_out, (size_t)tot.f_chunks_narrow * sizeof(NNChunk)));
+    for (size_t i = 0; i < out.size(); ++i) { out_slot[i] = out[i].slot; out_count[i] = out[i].count; out_begin[i] = out[i].begin; }
+    ISO_HIP_CHECK(copy_d2h(out_list, d_list.p, (size_t)total * 4));
+    if (tot.n_small) {
+        ISO_HIP_CHECK(copy_d2h(out_pa, d_pa.p, (size_t)tot.n_small * 4));
+        ISO_HIP_CHECK(copy_d2h(out_pb, d_pb.p, (size_t)tot.n_small * 4));
+    }
+    return ISOCON_OK;
+}
+
 #include "nn_context.inc"
 #include "nn_bounds.inc"
 #include "nn_lists.inc"

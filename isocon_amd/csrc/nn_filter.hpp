@@ -312,6 +312,21 @@ __global__ __launch_bounds__(256, 3) void k_nn_block_filter2(const uint32_t *__r
     }
 }
 
+// The filter's launches over the chunks in chunks_in (wide at [0 ..), narrow at [cap_in ..); their numbers in totals->n_chunks / n_chunks_narrow are
+// only known on the device, hence a work queue): the first pass, and the second one when it has a task array (tasks == nullptr: one pass).
+// The one place that launches the two kernels -- NNContext::plan_lists and the test entry isocon_block_filter_chunks both come here.
+inline hipError_t nnf_launch_filter(const uint32_t *text, uint32_t stride, const int32_t *lens, const uint32_t *meta, int32_t kcap, uint32_t *list, const NNChunk *chunks_in,
+                                    unsigned long long cap_in, NNChunk *chunks_out, unsigned long long cap_out, uint32_t *pa, uint32_t *pb, unsigned long long small_cap,
+                                    NNPlanTotals *totals, uint32_t list_min, NNFTask *tasks, unsigned long long tasks_cap)
+{
+    hipLaunchKernelGGL(k_nn_block_filter, dim3(NNF_GRID), dim3(256), 0, 0, text, stride, lens, meta, kcap, list, chunks_in, cap_in, chunks_out, cap_out, pa, pb, small_cap, totals, list_min,
+                       tasks, tasks_cap);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || tasks == nullptr) return e;
+    hipLaunchKernelGGL(k_nn_block_filter2, dim3(NNF_GRID2), dim3(256), 0, 0, text, stride, lens, meta, kcap, list, tasks, tasks_cap, pa, pb, small_cap, totals);
+    return hipGetLastError();
+}
+
 // Few chunks left (the filter rejected nearly everything): a table launch of a few dozen workgroups is one lone wave per SIMD for the length of
 // a whole chunk (1.4 ms for 57 000 pairs at C3), the pair-per-lane kernel takes the same pairs in 0.15 ms.  One workgroup per chunk appends
 // its pairs to the flat arrays (the host adds f_listed to its count of them).

@@ -54,15 +54,9 @@ int NNContext::plan_lists(const QMap &Q, uint32_t nq, const NNParams &PR, ListPl
     if (filter) {
         // one launch over a work queue of the builder's chunks (their number is only known on the device)
         tm.mark();
-        hipLaunchKernelGGL(k_nn_block_filter, dim3(NNF_GRID), dim3(256), 0, 0, d_text2.as<uint32_t>(), text2_stride, st->dev.lens, d_lmeta.as<uint32_t>(), PR.kcap, d_list.as<uint32_t>(),
-                           built, cap_in, L.a, cap_out, d_lpa.as<uint32_t>(), d_lpb.as<uint32_t>(), pairs_cap, d_ltot.as<NNPlanTotals>(), list_min,
-                           second ? d_ltasks.as<NNFTask>() : (NNFTask *)nullptr, tasks_cap);
-        ISO_HIP_CHECK(hipGetLastError());
-        if (second) {
-            hipLaunchKernelGGL(k_nn_block_filter2, dim3(NNF_GRID2), dim3(256), 0, 0, d_text2.as<uint32_t>(), text2_stride, st->dev.lens, d_lmeta.as<uint32_t>(), PR.kcap,
-                               d_list.as<uint32_t>(), d_ltasks.as<NNFTask>(), tasks_cap, d_lpa.as<uint32_t>(), d_lpb.as<uint32_t>(), pairs_cap, d_ltot.as<NNPlanTotals>());
-            ISO_HIP_CHECK(hipGetLastError());
-        }
+        ISO_HIP_CHECK(nnf_launch_filter(d_text2.as<uint32_t>(), text2_stride, st->dev.lens, d_lmeta.as<uint32_t>(), PR.kcap, d_list.as<uint32_t>(), built, cap_in, L.a, cap_out,
+                                        d_lpa.as<uint32_t>(), d_lpb.as<uint32_t>(), pairs_cap, d_ltot.as<NNPlanTotals>(), list_min,
+                                        second ? d_ltasks.as<NNFTask>() : (NNFTask *)nullptr, tasks_cap));
     }
     tm.stop_later(&stats.list_kernel_ms, &stats.filter_kernel_ms);          // (the filter's part of list_kernel_ms; the context's own marked time is narrow_kernel_ms)
     // (the interval closes in front of the copy of the totals, not behind it as it used to: list_kernel_ms is the kernels' time alone)

@@ -187,6 +187,38 @@ class SeqStore(object):
         _lib.check(self._L.isocon_block_bound_pairs(self._h, _ptr(a, _lib.u32p), _ptr(b, _lib.u32p), len(a), probe_stride, _ptr(out, _lib.i32p)), "isocon_block_bound_pairs")
         return out
 
+    def block_filter_chunks(self, thr, owner, narrow, chunk_ptr, words, kcap, list_min, second_pass):
+        """The main pass's two filter kernels on caller-made chunks (isocon_block_filter_chunks; tests).  thr[n]: per-entry thresholds 0 .. 64;
+        chunk c: owner[c], narrow[c], list words words[chunk_ptr[c]:chunk_ptr[c + 1]].  Returns a dict: `chunks` -- what is left for the tables,
+        (narrow, owner, list words) per chunk, the words in no defined order --, `pa`, `pb` -- the flat pairs, in no defined order --, and the
+        counters f_chunks, f_chunks_narrow, n_small, f_rejected, f_rejected2, f_listed, f_narrow_listed, f_tasks, overflow."""
+        thr = np.ascontiguousarray(thr, dtype=np.int32)
+        owner = np.ascontiguousarray(owner, dtype=np.uint32)
+        narrow = np.ascontiguousarray(narrow, dtype=np.uint8)
+        chunk_ptr = np.ascontiguousarray(chunk_ptr, dtype=np.uint64)
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        nc = len(owner)
+        if len(thr) != self.n or len(narrow) != nc or len(chunk_ptr) != nc + 1 or int(chunk_ptr[-1]) != len(words):
+            raise ValueError("chunk arrays disagree in length")
+        total = len(words)
+        slot = np.zeros(max(nc, 1), dtype=np.uint32)
+        count = np.zeros(max(nc, 1), dtype=np.uint32)
+        begin = np.zeros(max(nc, 1), dtype=np.uint64)
+        lst = np.zeros(max(total, 1), dtype=np.uint32)
+        pa = np.zeros(max(total, 1), dtype=np.uint32)
+        pb = np.zeros(max(total, 1), dtype=np.uint32)
+        ctr = np.zeros(9, dtype=np.uint64)
+        _lib.check(self._L.isocon_block_filter_chunks(self._h, _ptr(thr, _lib.i32p), nc, _ptr(owner, _lib.u32p), _ptr(narrow, _lib.u8p), _ptr(chunk_ptr, _lib.u64p),
+                                                      _ptr(words, _lib.u32p), int(kcap), int(list_min), int(second_pass), _ptr(slot, _lib.u32p), _ptr(count, _lib.u32p),
+                                                      _ptr(begin, _lib.u64p), nc, _ptr(lst, _lib.u32p), total, _ptr(pa, _lib.u32p), _ptr(pb, _lib.u32p), total,
+                                                      _ptr(ctr, _lib.u64p)), "isocon_block_filter_chunks")
+        names = ("f_chunks", "f_chunks_narrow", "n_small", "f_rejected", "f_rejected2", "f_listed", "f_narrow_listed", "f_tasks", "overflow")
+        out = {k: int(v) for k, v in zip(names, ctr)}
+        nw = out["f_chunks"]
+        out["chunks"] = [(int(i >= nw), int(slot[i]), lst[int(begin[i]):int(begin[i]) + int(count[i])].copy()) for i in range(nw + out["f_chunks_narrow"])]
+        out["pa"], out["pb"] = pa[:out["n_small"]], pb[:out["n_small"]]
+        return out
+
     def qgram_bound_matrix(self, q_begin=0, q_end=None, q_stride=1, depth=2 ** 32, q_block=1):
         """The bound matrix the NN main pass consults for the shard (q_begin, q_end, q_stride, q_block) (isocon_qgram_bound_matrix; tests):
         (row_ptr[rows + 1], bytes) -- row r = the shard's r-th entry (shard_entries) against the entries behind it within 63 of its length."""

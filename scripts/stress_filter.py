@@ -7,6 +7,7 @@ import numpy as np
 from isocon_amd import synth
 from isocon_amd.store import SeqStore
 from oracle import oracle as O
+from tests.filter_chunk_cases import STRESS_GENERATORS
 
 rng = random.Random(int(sys.argv[1]) if len(sys.argv) > 1 else 1)
 ncases = int(sys.argv[2]) if len(sys.argv) > 2 else 120
@@ -18,35 +19,8 @@ for case in range(ncases):
         n, L, iso = rng.randint(200, 3000), rng.choice([40, 63, 64, 65, 130, 255, 256, 257, 272, 500, 1000, 2500]), rng.randint(1, 6)
         prof = dict(synth.CCS_PROFILE, rate=rng.choice([0.002, 0.005, 0.01, 0.02, 0.04, 0.08]))
         seqs = synth.make_reads(n, L, iso, seed=rng.randint(0, 10 ** 6), profile=prof)[1]
-    elif kind == "lowc":
-        n, L = rng.randint(200, 1500), rng.randint(60, 900)
-        base = "".join(rng.choice("AC") for _ in range(L))
-        seqs = []
-        for i in range(n):
-            s = list(base)
-            for _ in range(rng.randint(0, 20)):
-                p = rng.randrange(len(s)); op = rng.random()
-                if op < 0.4: s[p] = rng.choice("AC")
-                elif op < 0.7: s.insert(p, rng.choice("AC"))
-                else: del s[p]
-            seqs.append("".join(s) or "A")
-    elif kind == "homo":
-        n = rng.randint(200, 1200)
-        runs = [(rng.choice("ACGT"), rng.randint(1, 14)) for _ in range(rng.randint(20, 120))]
-        seqs = []
-        for i in range(n):
-            seqs.append("".join(c * max(1, l + rng.choice([0, 0, 0, 1, -1])) for c, l in runs))
     else:
-        n = rng.randint(100, 800)
-        L = rng.choice([19, 20, 21, 35, 36, 37, 255, 256, 257, 271, 272, 273])
-        base = "".join(rng.choice("ACGT") for _ in range(L))
-        seqs = []
-        for i in range(n):
-            s = list(base)
-            for _ in range(rng.randint(0, 4)):
-                p = rng.randrange(len(s)); s[p] = rng.choice("ACGT")
-            if rng.random() < 0.3: s.insert(rng.randrange(len(s)), rng.choice("ACGT"))
-            seqs.append("".join(s))
+        seqs = STRESS_GENERATORS[kind](rng)          # lowc, homo, edges: shared with tests/test_gpu_filter_chunks.py, which runs a fixed-seed slice
     seqs = sorted(dict.fromkeys(seqs), key=len)
     if len(seqs) < 2:
         continue
