@@ -54,6 +54,27 @@ struct QMap {
     __host__ __device__ __forceinline__ bool same(const QMap &o) const { return begin == o.begin && end == o.end && stride == o.stride && block_log2 == o.block_log2; }
 };
 
+// 16 bits -> the even bits of a dword
+__device__ __forceinline__ uint32_t spread16(uint32_t x)
+{
+    x = (x | (x << 8)) & 0x00ff00ffu;
+    x = (x | (x << 4)) & 0x0f0f0f0fu;
+    x = (x | (x << 2)) & 0x33333333u;
+    x = (x | (x << 1)) & 0x55555555u;
+    return x;
+}
+
+// Dword j of sequence i's 2-bit text (nn_filter.hpp): the bases 16 j .. 16 j + 15, base b at bits 2b, 2b + 1; 0 from the sequence's end
+// on (bases past the end are 0 in the planes).  The one packing expression of k_build_text2 and k_qgram_profile4.
+__device__ __forceinline__ uint32_t text2_word(const DevStore &S, uint32_t i, int32_t len, uint32_t j)
+{
+    const int32_t c0 = (int32_t)j * 16;
+    if (c0 >= len) return 0u;
+    const size_t at = ((size_t)(c0 >> 6) * S.n + i) * 2;
+    const uint32_t lo = (uint32_t)(S.planes[at] >> (c0 & 63)) & 0xffffu, hi = (uint32_t)(S.planes[at + 1] >> (c0 & 63)) & 0xffffu;
+    return spread16(lo) | (spread16(hi) << 1);
+}
+
 extern thread_local std::string g_last_error;
 
 #define ISO_HIP_CHECK(expr)                                                                    \

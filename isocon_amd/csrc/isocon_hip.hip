@@ -72,8 +72,9 @@ static const char *variant_value(const char *name)
 
 // What the pool's nearest-neighbour slots currently hold, next to the slots themselves (no free-floating state: a store reaches it
 // through its pool, and whoever overwrites or releases a slot invalidates the tag in the same place).
-// BoundTag: the q-gram bound matrix of the last seed phase (slots SLOT_NN_LB / SLOT_NN_LBROW): the main phase of the SAME store and
-// shard that follows uses it instead of computing it again.  Identified by the store's serial number (not its address).
+// BoundTag: the q-gram bound matrix of the last seed phase (slot SLOT_NN_LB; its row offsets and row lengths inside SLOT_NN_LBCHUNKS, where
+// lb_row and lb_len point): the main phase of the SAME store and shard that follows uses it instead of computing it again.  Identified
+// by the store's serial number (not its address).
 struct BoundTag {
     bool valid = false, has_order = false;
     uint64_t serial = 0;
@@ -81,6 +82,8 @@ struct BoundTag {
     uint32_t depth = 0;
     int32_t kcap = 0;
     unsigned long long lb_total = 0;
+    const unsigned long long *lb_row = nullptr;
+    const uint32_t *lb_len = nullptr;
 };
 // MsaBuilt: the matrices a build left in SLOT_MSA_IN (their partition tables in SLOT_MSA_PART .. SLOT_MSA_CBASE) for the correction that
 // follows, with the host's copy of their layout.  `by`: which entry point built them -- isocon_msa_correct_built / isocon_msa_read_built pair
@@ -128,12 +131,12 @@ struct ScratchPool {
 
 enum {
     SLOT_ED_TS = 0, SLOT_ED_IDS, SLOT_ED_K, SLOT_ED_OUT, SLOT_FULL_A, SLOT_FULL_B, SLOT_FULL_K, SLOT_FULL_OUT,
-    SLOT_NN_BEST, SLOT_NN_QF, SLOT_NN_TF, SLOT_NN_HITS, SLOT_NN_HITCOUNT, SLOT_NN_STATS, SLOT_NN_TS, SLOT_NN_IDS, SLOT_NN_PLANES2, SLOT_NN_PERM, SLOT_NN_IL, SLOT_NN_IL2, SLOT_NN_HITS2, SLOT_NN_HITCOUNT2, SLOT_NN_QPROF, SLOT_NN_QSUM, SLOT_NN_LB, SLOT_NN_LBROW, SLOT_NN_LBLEN, SLOT_NN_SLOTORDER, SLOT_NN_LBCHUNKS, SLOT_NN_ROWMIN, SLOT_NN_COLMIN, SLOT_NN_SEED_A, SLOT_NN_SEED_B, SLOT_NN_SEED_N, SLOT_NN_LBT, SLOT_NN_LBT_OFF, SLOT_NN_LBT_SLO, SLOT_NN_LBT_LEN, SLOT_NN_LBT_PAD, SLOT_NN_SCORE, SLOT_NN_LDEST, SLOT_NN_FIN_HITS, SLOT_NN_FIN_CNT, SLOT_NN_FIN_START, SLOT_NN_FIN_CUR, SLOT_NN_FIN_NB, SLOT_NN_FIN_LEN2, SLOT_NN_FIN_OUT, SLOT_NN_FIN_FLAG, SLOT_NN_FIN_BEST, SLOT_NN_ACC_HITS, SLOT_NN_LTOT, SLOT_NN_LCHUNKS, SLOT_NN_LIST, SLOT_NN_LPA, SLOT_NN_LPB, SLOT_NN_TEXT2, SLOT_NN_LTASKS, SLOT_NN_RECORD,
+    SLOT_NN_BEST, SLOT_NN_QF, SLOT_NN_TF, SLOT_NN_HITS, SLOT_NN_HITCOUNT, SLOT_NN_STATS, SLOT_NN_TS, SLOT_NN_IDS, SLOT_NN_PLANES2, SLOT_NN_PERM, SLOT_NN_IL, SLOT_NN_IL2, SLOT_NN_HITS2, SLOT_NN_HITCOUNT2, SLOT_NN_QPROF, SLOT_NN_QSUM, SLOT_NN_LB, SLOT_NN_SLOTORDER, SLOT_NN_LBCHUNKS, SLOT_NN_ROWMIN, SLOT_NN_COLMIN, SLOT_NN_SEED_A, SLOT_NN_SEED_B, SLOT_NN_SEED_N, SLOT_NN_LBT, SLOT_NN_LBT_OFF, SLOT_NN_LBT_SLO, SLOT_NN_LBT_LEN, SLOT_NN_LBT_PAD, SLOT_NN_SCORE, SLOT_NN_LDEST, SLOT_NN_FIN_HITS, SLOT_NN_FIN_CNT, SLOT_NN_FIN_START, SLOT_NN_FIN_CUR, SLOT_NN_FIN_NB, SLOT_NN_FIN_LEN2, SLOT_NN_FIN_OUT, SLOT_NN_FIN_FLAG, SLOT_NN_FIN_BEST, SLOT_NN_ACC_HITS, SLOT_NN_LTOT, SLOT_NN_LCHUNKS, SLOT_NN_LIST, SLOT_NN_LPA, SLOT_NN_LPB, SLOT_NN_TEXT2, SLOT_NN_LTASKS, SLOT_NN_RECORD,
     SLOT_NN2_STATE, SLOT_NN2_TPOS, SLOT_NN2_EXC, SLOT_NN2_CTR, SLOT_NN2_PAIRS, SLOT_NN2_WIDE,
     SLOT_SG_PAIRS, SLOT_SG_R, SLOT_SG_TRACE, SLOT_SG_END, SLOT_SG_OPS, SLOT_SG_CNT, SLOT_SG_RES, SLOT_SG_OFF, SLOT_SG_DENSE, SLOT_SG_BOUND, SLOT_SG_AOFF, SLOT_SG_ALNA, SLOT_SG_ALNB,
     SLOT_MSA_IN, SLOT_MSA_OUT, SLOT_MSA_DEG, SLOT_MSA_COUNTS, SLOT_MSA_MAJ, SLOT_MSA_FLAGS, SLOT_MSA_TOT, SLOT_MSA_NCAND, SLOT_MSA_LEN, SLOT_MSA_OFF, SLOT_MSA_PACKED, SLOT_MSA_ROWS, SLOT_MSA_OPS, SLOT_MSA_OPTR, SLOT_MSA_LONGEST, SLOT_MSA_WIDTH, SLOT_MSA_CSLOT, SLOT_MSA_LTOT, SLOT_MSA_WIDE, SLOT_MSA_PROW, SLOT_MSA_PCOL, SLOT_MSA_PPTR, SLOT_MSA_PBYTES, SLOT_MSA_PART, SLOT_MSA_FIRST, SLOT_MSA_LM, SLOT_MSA_SBASE, SLOT_MSA_NCOLS, SLOT_MSA_MOFF, SLOT_MSA_CBASE, SLOT_MSA_CBP, SLOT_MSA_CBC, SLOT_MSA_CBR,
     SLOT_HW_Q, SLOT_HW_T, SLOT_HW_K, SLOT_HW_OUT, SLOT_HW_TRACE, SLOT_HW_CTR, SLOT_HW_TILEQ, SLOT_HW_LANES, SLOT_HW_PQ, SLOT_HW_KEY, SLOT_HW_HIST, SLOT_HW_CURSOR, SLOT_HW_TBASE, SLOT_HW_CLS,
-    SLOT_PACK_ASCII, SLOT_PACK_OFF, SLOT_PACK_BAD, SLOT_PACK_HIST, SLOT_PACK_FLAGS, SLOT_EB_A, SLOT_EB_B, SLOT_EB_K, SLOT_EB_OUT, SLOT_EB_ROWS, SLOT_SCAN_TMP, SLOT_SCAN_SUMS,
+    SLOT_PACK_ASCII, SLOT_PACK_OFF, SLOT_PACK_BAD, SLOT_PACK_HIST, SLOT_PACK_FLAGS, SLOT_EB_A, SLOT_EB_B, SLOT_EB_K, SLOT_EB_OUT, SLOT_EB_ROWS, SLOT_SCAN_TMP, SLOT_SCAN_SUMS, SLOT_SCAN_TMP_SIDE, SLOT_SCAN_SUMS_SIDE,
     SLOT_RT_REF, SLOT_RT_IN, SLOT_RT_OUT,
     SLOT_EV_IN, SLOT_EV_OUT, SLOT_EV_SNIP,
     SLOT_PB_IN, SLOT_PB_OUT,
@@ -252,7 +255,8 @@ static hipError_t copy_h2d(void *ddst, const void *src, size_t bytes)
 }
 
 // The one side stream of the library: the row layout of the bound matrix (NNContext::build_bounds) goes up on it from pinned memory of
-// its own while the profile kernel runs on the null stream, which then waits for `done` instead of the host waiting for three copies.
+// its own while the profile kernel runs on the null stream, followed by the small launches and fills that only depend on it (the
+// transposed matrix' row layout, the seed arrays); the null stream then waits for `done` once, in front of k_qgram_mm.
 // Like g_stage it is the process' only one and takes no lock: one process drives one device and runs one search at a time.
 struct SideUpload {
     hipStream_t stream = nullptr;
@@ -312,16 +316,17 @@ struct DevBuf {
     }
 };
 
-// out[0 .. n] = exclusive prefix sums of f(in[i]) (common.hpp: k_scan_tiles + k_scan_finish), on the null stream
+// out[0 .. n] = exclusive prefix sums of f(in[i]) (common.hpp: k_scan_tiles + k_scan_finish), on `stream`.  A scan on another stream than
+// the null stream has scratch slots of its own: one on the null stream may be in flight at the same time.
 template <int SHIFT, class OUT>
-static int device_exscan(ScratchPool *pl, const uint32_t *d_in, uint32_t n, OUT *d_out)
+static int device_exscan(ScratchPool *pl, const uint32_t *d_in, uint32_t n, OUT *d_out, hipStream_t stream = 0)
 {
-    DevBuf d_tmp(pl, SLOT_SCAN_TMP), d_sums(pl, SLOT_SCAN_SUMS);
+    DevBuf d_tmp(pl, stream ? SLOT_SCAN_TMP_SIDE : SLOT_SCAN_TMP), d_sums(pl, stream ? SLOT_SCAN_SUMS_SIDE : SLOT_SCAN_SUMS);
     const uint32_t tiles = std::max<uint32_t>(1, (n + SCAN_TILE - 1) / SCAN_TILE);
     int rc;
     if ((rc = d_tmp.alloc((size_t)std::max<uint32_t>(n, 1) * 4)) || (rc = d_sums.alloc((size_t)tiles * 8))) return rc;
-    hipLaunchKernelGGL((k_scan_tiles<SHIFT>), dim3(tiles), dim3(256), 0, 0, d_in, n, d_tmp.as<uint32_t>(), d_sums.as<unsigned long long>());
-    hipLaunchKernelGGL((k_scan_finish<OUT>), dim3(tiles), dim3(256), 0, 0, d_tmp.as<uint32_t>(), n, d_sums.as<unsigned long long>(), tiles, d_out, (unsigned long long *)nullptr);
+    hipLaunchKernelGGL((k_scan_tiles<SHIFT>), dim3(tiles), dim3(256), 0, stream, d_in, n, d_tmp.as<uint32_t>(), d_sums.as<unsigned long long>());
+    hipLaunchKernelGGL((k_scan_finish<OUT>), dim3(tiles), dim3(256), 0, stream, d_tmp.as<uint32_t>(), n, d_sums.as<unsigned long long>(), tiles, d_out, (unsigned long long *)nullptr);
     ISO_HIP_CHECK(hipGetLastError());
     return ISOCON_OK;
 }
@@ -1085,7 +1090,8 @@ int qgram_bounds_for_pairs(isocon_store *s, const uint32_t *a, const uint32_t *b
     ISO_HIP_CHECK(copy_h2d(d_b.p, b, n_pairs * 4));
     EventTimer tm;
     tm.start();
-    hipLaunchKernelGGL(k_qgram_profile4, dim3((n + QP_SEQS - 1) / QP_SEQS), dim3(256), 0, 0, s->dev, d_prof.as<uint8_t>(), d_sum.as<uint32_t>(), n_pad);
+    hipLaunchKernelGGL(k_qgram_profile4, dim3((n + QP_SEQS - 1) / QP_SEQS), dim3(256), 0, 0, s->dev, d_prof.as<uint8_t>(), d_sum.as<uint32_t>(), n_pad,
+                       (uint32_t *)nullptr, 0u);
     ISO_HIP_CHECK(hipGetLastError());
     // (a launch holds fewer than 2^32 threads: 2^24 pairs per launch)
     for (uint64_t at = 0; at < n_pairs; at += (uint64_t)1 << 24) {

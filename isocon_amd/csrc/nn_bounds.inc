@@ -13,7 +13,8 @@ int NNContext::build_bounds(const QMap &Q, int32_t kcap, NNParams &P, bool want_
         st->pool.bound_tag.depth == depth && st->pool.bound_tag.kcap == kcap) {
         // the seed phase of this very store and shard left the matrix in the pool (isocon_nn_partial phase 0 -> phase 1)
         P.lb = static_cast<const uint8_t *>(st->pool.slots[SLOT_NN_LB].p);
-        P.lb_row = static_cast<const unsigned long long *>(st->pool.slots[SLOT_NN_LBROW].p);
+        P.lb_row = lb_row_dev = st->pool.bound_tag.lb_row;
+        lb_len_dev = st->pool.bound_tag.lb_len;
         if (st->pool.bound_tag.has_order && use_slot_order(Q.count())) P.slot_order = static_cast<const uint32_t *>(st->pool.slots[SLOT_NN_SLOTORDER].p);
         lb_total = st->pool.bound_tag.lb_total;
         return ISOCON_OK;
@@ -32,13 +33,57 @@ int NNContext::build_bounds(const QMap &Q, int32_t kcap, NNParams &P, bool want_
         if (!free_mem(free_b) || prof_bytes > free_b / 2 + st->pool.slots[SLOT_NN_QPROF].cap) return ISOCON_OK;
         if (d_qprof.alloc(prof_bytes) || d_qsum.alloc((size_t)n * 4)) return ISOCON_OK;
     }
+    // the step is going to run the block filter: the profile kernel writes its 2-bit texts on the way (no room for them: plan_lists finds
+    // none either and runs without the filter)
+    uint32_t *text2 = !text2_ready && filter_wanted() && text2_room() ? d_text2.as<uint32_t>() : nullptr;
     bclk.lap("bounds: memory check + profile buffers");
-    // (the side stream's uploads below start behind everything the null stream holds at this point, not behind the profile kernel)
+    // What an earlier call left on the side stream is through before anything below is enqueued.  The side stream's work below starts
+    // behind everything the null stream holds at this point, not behind the profile kernel.
+    g_side.settle();
     const bool side = !variant("nn_sync_uploads") && g_side.ready() && hipEventRecord(g_side.before, 0) == hipSuccess;
     tm.start();
-    hipLaunchKernelGGL(k_qgram_profile4, dim3((n + QP_SEQS - 1) / QP_SEQS), dim3(256), 0, 0, st->dev, d_qprof.as<uint8_t>(), d_qsum.as<uint32_t>(), n_pad);
+    hipLaunchKernelGGL(k_qgram_profile4, dim3((n + QP_SEQS - 1) / QP_SEQS), dim3(256), 0, 0, st->dev, d_qprof.as<uint8_t>(), d_qsum.as<uint32_t>(), n_pad,
+                       text2, text2_stride);
     ISO_HIP_CHECK(hipGetLastError());
+    if (text2) text2_ready = true;
     struct StopTimer { NNContext &c; bool armed = true; ~StopTimer() { if (armed) c.tm.stop_later(&c.stats.bound_kernel_ms); } } stop_timer{*this};
+    // Everything between the profile kernel and k_qgram_mm that neither of them writes or reads goes on the side stream while the
+    // profile kernel runs.  At once, while the host lays out the rows: the fills that are sized from n alone -- the hub scores, the
+    // row / column minima, the seed arrays of run_bound_seeds and their counter.  Behind the host's loops: row lengths, tile table and
+    // row offsets (staged in pinned memory) and the transposed matrix' row layout (k_lbt_rows, its scan, k_lbt_offsets).  The null
+    // stream waits for all of it once, in front of k_qgram_mm; the host does not wait at all.  Without a side stream the same
+    // operations go on the null stream, the uploads as three blocking copies.
+    hipStream_t ls = 0;          // the stream of the fills and the row layout
+    // an early return between the first side-stream operation and the null stream's wait leaves nothing in flight behind it
+    struct SideGuard { bool armed = false; ~SideGuard() { if (armed) g_side.settle(); } } side_guard;
+    if (side) {
+        g_side.in_flight = side_guard.armed = true;          // (from the first operation on: an error below must not let the next call write the pinned block, or a buffer of the pool, unsettled)
+        ISO_HIP_CHECK(hipStreamWaitEvent(g_side.stream, g_side.before, 0));
+        ls = g_side.stream;
+    }
+    d_score.pool = &st->pool;
+    d_score.slot = SLOT_NN_SCORE;
+    if (d_score.alloc((size_t)n * 4)) return ISOCON_OK;
+    QMFills fills = {};
+    fills.r[0] = {d_score.as<uint32_t>(), n, 0u};
+    unsigned long long *rowmin = nullptr, *colmin = nullptr;
+    if (want_seeds) {
+        const uint64_t n_seed_words = (uint64_t)2 * QM_SEEDS * n;          // dwords of each of the two seed arrays (run_bound_seeds: np)
+        d_rowmin.pool = d_colmin.pool = d_seed_a.pool = d_seed_b.pool = d_seed_n.pool = &st->pool;
+        d_rowmin.slot = SLOT_NN_ROWMIN; d_colmin.slot = SLOT_NN_COLMIN; d_seed_a.slot = SLOT_NN_SEED_A; d_seed_b.slot = SLOT_NN_SEED_B; d_seed_n.slot = SLOT_NN_SEED_N;
+        if (!(d_rowmin.alloc((size_t)nq * 8 * QM_SEEDS) || d_colmin.alloc((size_t)n_pad * 8 * QM_SEEDS) || d_seed_a.alloc((size_t)n_seed_words * 4) || d_seed_b.alloc((size_t)n_seed_words * 4) ||
+              d_seed_n.alloc(8))) {
+            fills.r[1] = {d_rowmin.as<uint32_t>(), (unsigned long long)nq * 2 * QM_SEEDS, 0xffffffffu};
+            fills.r[2] = {d_colmin.as<uint32_t>(), (unsigned long long)n_pad * 2 * QM_SEEDS, 0xffffffffu};
+            fills.r[3] = {d_seed_a.as<uint32_t>(), n_seed_words, 0xffffffffu};
+            fills.r[4] = {d_seed_b.as<uint32_t>(), n_seed_words, 0xffffffffu};
+            fills.r[5] = {d_seed_n.as<uint32_t>(), 2, 0u};
+            rowmin = d_rowmin.as<unsigned long long>();
+            colmin = d_colmin.as<unsigned long long>();
+        }
+    }
+    hipLaunchKernelGGL(k_qm_fills, dim3(1024), dim3(256), 0, ls, fills);
+    ISO_HIP_CHECK(hipGetLastError());
     // Row s of the matrix = launch slot s of the main pass = entry q = Q.entry(s), its columns the neighbours
     // p = q + 1 .. q + rlen[s]; the kernels address column p as lb[off[s] + (p - q - 1)].  A row's storage starts at a 16-byte
     // boundary with column (q + 1) & ~15 and ends with column ((q + rlen) | 15), so the address of column p is congruent to
@@ -102,48 +147,42 @@ int NNContext::build_bounds(const QMap &Q, int32_t kcap, NNParams &P, bool want_
     while (tiles.size() % 256) tiles.push_back(make_uint2(0xffffffffu, 0xffffffffu));
     if (tiles.size() > 0x7fffffffull) return ISOCON_OK;
     bclk.lap("bounds: tile table (host)");
-    d_lb.pool = d_lbrow.pool = d_lblen.pool = &st->pool;
-    d_lb.slot = SLOT_NN_LB; d_lbrow.slot = SLOT_NN_LBROW; d_lblen.slot = SLOT_NN_LBLEN;
+    d_lb.pool = &st->pool;
+    d_lb.slot = SLOT_NN_LB;
     int rc;
-    if ((rc = d_lb.alloc((size_t)total + 16)) ||          // (16 spare bytes, as behind the transposed matrix: the list builder reads whole dwords at a row's end)
-        (rc = d_lbrow.alloc((size_t)nq * 8)) || (rc = d_lblen.alloc((size_t)nq * 4)))
-        return ISOCON_OK;          // no room: the pass runs without bounds
-    d_lbt.pool = d_offT.pool = d_sloT.pool = d_lenT.pool = d_score.pool = &st->pool;
-    d_lbt.slot = SLOT_NN_LBT; d_offT.slot = SLOT_NN_LBT_OFF; d_sloT.slot = SLOT_NN_LBT_SLO; d_lenT.slot = SLOT_NN_LBT_LEN; d_score.slot = SLOT_NN_SCORE;
+    if ((rc = d_lb.alloc((size_t)total + 16))) return ISOCON_OK;          // no room: the pass runs without bounds (16 spare bytes, as behind the transposed matrix: the list builder reads whole dwords at a row's end)
+    d_lbt.pool = d_offT.pool = d_sloT.pool = d_lenT.pool = &st->pool;
+    d_lbt.slot = SLOT_NN_LBT; d_offT.slot = SLOT_NN_LBT_OFF; d_sloT.slot = SLOT_NN_LBT_SLO; d_lenT.slot = SLOT_NN_LBT_LEN;
     DevBuf d_padT(&st->pool, SLOT_NN_LBT_PAD);
-    if (d_lbt.alloc((size_t)totalT + 16) || d_offT.alloc(((size_t)n + 1) * 8) || d_sloT.alloc((size_t)n * 4) || d_lenT.alloc((size_t)n * 4) || d_score.alloc((size_t)n * 4) ||
+    if (d_lbt.alloc((size_t)totalT + 16) || d_offT.alloc(((size_t)n + 1) * 8) || d_sloT.alloc((size_t)n * 4) || d_lenT.alloc((size_t)n * 4) ||
         d_padT.alloc((size_t)n * 4))
         return ISOCON_OK;
-    ISO_HIP_CHECK(hipMemsetAsync(d_score.p, 0, (size_t)n * 4, 0));
     d_chunks.pool = &st->pool;
     d_chunks.slot = SLOT_NN_LBCHUNKS;
-    if (d_chunks.alloc(tiles.size() * sizeof(uint2))) return ISOCON_OK;
-    // tile table, row offsets and row lengths: staged in pinned memory and copied on the side stream while the profile kernel runs; the
-    // null stream waits for them in front of k_lbt_rows, the host does not wait at all
+    // tile table, row offsets and row lengths: one buffer on the device, laid out like the pinned block, so that they go up in ONE copy
+    // (three copies on the side stream took 70 us from the first start to the last end, 28 us of them copying)
     const size_t b_tiles = (tiles.size() * sizeof(uint2) + 15) & ~(size_t)15, b_off = ((size_t)nq * 8 + 15) & ~(size_t)15, b_len = (size_t)nq * 4;
+    if (d_chunks.alloc(b_tiles + b_off + b_len)) return ISOCON_OK;
+    unsigned long long *const d_lbrow = reinterpret_cast<unsigned long long *>(d_chunks.as<char>() + b_tiles);
+    uint32_t *const d_lblen = reinterpret_cast<uint32_t *>(d_chunks.as<char>() + b_tiles + b_off);
     char *pin = nullptr;
-    if (side) { g_side.settle(); pin = static_cast<char *>(g_side.pinned.get(b_tiles + b_off + b_len)); }
+    if (side) pin = static_cast<char *>(g_side.pinned.get(b_tiles + b_off + b_len));
     if (pin) {
         memcpy(pin, tiles.data(), tiles.size() * sizeof(uint2));
         memcpy(pin + b_tiles, off.data(), (size_t)nq * 8);
         memcpy(pin + b_tiles + b_off, rlen.data(), (size_t)nq * 4);
-        g_side.in_flight = true;          // (from the first copy on: an error below must not let the next call write the block unsettled)
-        ISO_HIP_CHECK(hipStreamWaitEvent(g_side.stream, g_side.before, 0));
-        ISO_HIP_CHECK(hipMemcpyAsync(d_chunks.p, pin, tiles.size() * sizeof(uint2), hipMemcpyHostToDevice, g_side.stream));
-        ISO_HIP_CHECK(hipMemcpyAsync(d_lbrow.p, pin + b_tiles, (size_t)nq * 8, hipMemcpyHostToDevice, g_side.stream));
-        ISO_HIP_CHECK(hipMemcpyAsync(d_lblen.p, pin + b_tiles + b_off, (size_t)nq * 4, hipMemcpyHostToDevice, g_side.stream));
-        ISO_HIP_CHECK(hipEventRecord(g_side.done, g_side.stream));
-        ISO_HIP_CHECK(hipStreamWaitEvent(0, g_side.done, 0));
+        ISO_HIP_CHECK(hipMemcpyAsync(d_chunks.p, pin, b_tiles + b_off + b_len, hipMemcpyHostToDevice, ls));
     } else {
         ISO_HIP_CHECK(copy_h2d(d_chunks.p, tiles.data(), tiles.size() * sizeof(uint2)));
-        ISO_HIP_CHECK(copy_h2d(d_lbrow.p, off.data(), (size_t)nq * 8));
-        ISO_HIP_CHECK(copy_h2d(d_lblen.p, rlen.data(), (size_t)nq * 4));
+        ISO_HIP_CHECK(copy_h2d(d_lbrow, off.data(), (size_t)nq * 8));
+        ISO_HIP_CHECK(copy_h2d(d_lblen, rlen.data(), (size_t)nq * 4));
     }
-    hipLaunchKernelGGL(k_lbt_rows, dim3((n + 255) / 256), dim3(256), 0, 0, Q, nq, d_lblen.as<uint32_t>(), n, d_sloT.as<uint32_t>(), d_lenT.as<uint32_t>(), d_padT.as<uint32_t>());
-    if ((rc = device_exscan<0, unsigned long long>(&st->pool, d_padT.as<uint32_t>(), n, d_offT.as<unsigned long long>()))) return ISOCON_OK;
-    hipLaunchKernelGGL(k_lbt_offsets, dim3((n + 255) / 256), dim3(256), 0, 0, n, d_sloT.as<uint32_t>(), d_offT.as<unsigned long long>());
+    hipLaunchKernelGGL(k_lbt_rows, dim3((n + 255) / 256), dim3(256), 0, ls, Q, nq, d_lblen, n, d_sloT.as<uint32_t>(), d_lenT.as<uint32_t>(), d_padT.as<uint32_t>());
+    if ((rc = device_exscan<0, unsigned long long>(&st->pool, d_padT.as<uint32_t>(), n, d_offT.as<unsigned long long>(), ls))) return ISOCON_OK;
+    hipLaunchKernelGGL(k_lbt_offsets, dim3((n + 255) / 256), dim3(256), 0, ls, n, d_sloT.as<uint32_t>(), d_offT.as<unsigned long long>());
     ISO_HIP_CHECK(hipGetLastError());
-    bclk.lap("bounds: alloc + uploads");
+    if (ls) ISO_HIP_CHECK(hipEventRecord(g_side.done, ls));
+    bclk.lap("bounds: alloc + uploads + row layout (enqueued)");
     if (use_slot_order(nq)) {
         // workgroup order of the main pass: widest windows first (stable sort by row length), so that the launch does
         // not end with a few long-running entries -- matters when a rank's share is only a few rounds of workgroups
@@ -155,26 +194,19 @@ int NNContext::build_bounds(const QMap &Q, int32_t kcap, NNParams &P, bool want_
         if (d_order.alloc((size_t)nq * 4)) return ISOCON_OK;
         ISO_HIP_CHECK(copy_h2d(d_order.p, order.data(), (size_t)nq * 4));
     }
-    unsigned long long *rowmin = nullptr, *colmin = nullptr;
-    if (want_seeds) {
-        d_rowmin.pool = d_colmin.pool = d_seed_a.pool = d_seed_b.pool = &st->pool;
-        d_rowmin.slot = SLOT_NN_ROWMIN; d_colmin.slot = SLOT_NN_COLMIN; d_seed_a.slot = SLOT_NN_SEED_A; d_seed_b.slot = SLOT_NN_SEED_B;
-        if (!(d_rowmin.alloc((size_t)nq * 8 * QM_SEEDS) || d_colmin.alloc((size_t)n_pad * 8 * QM_SEEDS) || d_seed_a.alloc((size_t)n * 8 * QM_SEEDS) || d_seed_b.alloc((size_t)n * 8 * QM_SEEDS))) {
-            ISO_HIP_CHECK(hipMemsetAsync(d_rowmin.p, 0xff, (size_t)nq * 8 * QM_SEEDS, 0));
-            ISO_HIP_CHECK(hipMemsetAsync(d_colmin.p, 0xff, (size_t)n_pad * 8 * QM_SEEDS, 0));
-            rowmin = d_rowmin.as<unsigned long long>();
-            colmin = d_colmin.as<unsigned long long>();
-        }
-    }
-    bclk.lap("bounds: slot order + seed buffers");
+    bclk.lap("bounds: slot order");
     static bool lds_attr_set = false;
     if (!lds_attr_set) {
         ISO_HIP_CHECK(hipFuncSetAttribute((const void *)k_qgram_mm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)QM_LDS_BYTES));
         lds_attr_set = true;
     }
+    if (ls) {
+        ISO_HIP_CHECK(hipStreamWaitEvent(0, g_side.done, 0));
+        side_guard.armed = false;
+    }
     tm.mark();          // (the contraction by itself: mm_kernel_ms)
     hipLaunchKernelGGL(k_qgram_mm, dim3((unsigned)tiles.size()), dim3(512), QM_LDS_BYTES, 0, d_qprof.as<uint8_t>(), d_qsum.as<uint32_t>(), n, n_pad,
-                       d_chunks.as<uint2>(), d_lbrow.as<unsigned long long>(), d_lblen.as<uint32_t>(), d_lb.as<uint8_t>(), Q, nq,
+                       d_chunks.as<uint2>(), d_lbrow, d_lblen, d_lb.as<uint8_t>(), Q, nq,
                        d_qf.as<uint8_t>(), d_tf.as<uint8_t>(), rowmin, colmin, d_offT.as<unsigned long long>(), d_sloT.as<uint32_t>(), d_lenT.as<uint32_t>(),
                        d_lbt.as<uint8_t>(), d_score.as<uint32_t>());
     ISO_HIP_CHECK(hipGetLastError());
@@ -203,13 +235,16 @@ int NNContext::build_bounds(const QMap &Q, int32_t kcap, NNParams &P, bool want_
 #endif
     for (const uint2 &t : tiles) stats.bound_tiles += t.x != 0xffffffffu;
     P.lb = d_lb.as<uint8_t>();
-    P.lb_row = d_lbrow.as<unsigned long long>();
+    P.lb_row = lb_row_dev = d_lbrow;
+    lb_len_dev = d_lblen;
     if (use_slot_order(nq)) P.slot_order = d_order.as<uint32_t>();
     seeds_ready = rowmin != nullptr;
     seed_nq = nq;
     lb_total = total;
     st->pool.bound_tag.valid = true;
     st->pool.bound_tag.lb_total = total;
+    st->pool.bound_tag.lb_row = d_lbrow;
+    st->pool.bound_tag.lb_len = d_lblen;
     st->pool.bound_tag.has_order = use_slot_order(nq);
     st->pool.bound_tag.serial = st->serial;
     st->pool.bound_tag.map = Q; st->pool.bound_tag.depth = depth; st->pool.bound_tag.kcap = kcap;
@@ -228,12 +263,7 @@ int NNContext::run_bound_seeds(const QMap &Q)
     uint32_t col_classes = QM_SEEDS;
     while (col_classes > 1 && col_classes * ranks > (uint32_t)QM_SEEDS) col_classes >>= 1;
     if (const char *e = variant_value("nn_seed_classes")) { const int v = atoi(e); if (v == 1 || v == 2 || v == QM_SEEDS) col_classes = (uint32_t)v; }      // A/B runs
-    DevBuf d_seed_n(&st->pool, SLOT_NN_SEED_N);
-    int rc;
-    if ((rc = d_seed_n.alloc(8))) return rc;
-    ISO_HIP_CHECK(hipMemsetAsync(d_seed_n.p, 0, 8, 0));
-    ISO_HIP_CHECK(hipMemsetAsync(d_seed_a.p, 0xff, (size_t)np * 4, 0));
-    ISO_HIP_CHECK(hipMemsetAsync(d_seed_b.p, 0xff, (size_t)np * 4, 0));
+    // (build_bounds filled the seed arrays and zeroed their counter on its way: seeds_ready says so)
     hipLaunchKernelGGL(k_qgram_seed_pairs, dim3((n + 255) / 256), dim3(256), 0, 0, d_rowmin.as<unsigned long long>(), d_colmin.as<unsigned long long>(),
                        n, Q, seed_nq, col_classes, d_seed_a.as<uint32_t>(), d_seed_b.as<uint32_t>(), d_seed_n.as<unsigned long long>());
     ISO_HIP_CHECK(hipGetLastError());

@@ -39,11 +39,13 @@ struct NNContext {
     DevBuf d_text;                 // nibble store of the lane-refill kernels (built on first use)
     uint32_t text_stride = 0;
     bool text_ready = false;
-    DevBuf d_qprof, d_qsum, d_lb, d_lbrow, d_lblen;   // q-gram profiles and the bound matrix of the main pass (qgram_mm.hpp)
-    DevBuf d_chunks;       // tile table of k_qgram_mm
+    DevBuf d_qprof, d_qsum, d_lb;   // q-gram profiles and the bound matrix of the main pass (qgram_mm.hpp)
+    DevBuf d_chunks;       // tile table of k_qgram_mm, with the matrix' row offsets and row lengths behind it (one buffer: one upload)
+    const unsigned long long *lb_row_dev = nullptr;
+    const uint32_t *lb_len_dev = nullptr;
     DevBuf d_lbt, d_offT, d_sloT, d_lenT, d_score;     // the transposed matrix, its row layout and the entries' hub scores
     DevBuf d_order;        // launch slots of the main pass, widest window first
-    DevBuf d_rowmin, d_colmin, d_seed_a, d_seed_b;   // smallest bounds per row / column and the seed pairs made of them
+    DevBuf d_rowmin, d_colmin, d_seed_a, d_seed_b, d_seed_n;   // smallest bounds per row / column, the seed pairs made of them and their number
     uint64_t hits_cap = 0;
     std::vector<int32_t> best;   // host mirror
     std::vector<int32_t> hits;   // host triples
@@ -90,19 +92,28 @@ struct NNContext {
         return true;
     }
     bool ensure_text() { return text_affordable() && build_text(); }
-    // 2-bit texts of the block filter (nn_filter.hpp), built on first use
+    // 2-bit texts of the block filter (nn_filter.hpp).  A step that builds its bounds has them written by the profile kernel
+    // (build_bounds asks filter_wanted() and text2_room() and sets text2_ready); a call that finds its bound matrix in the pool
+    // (bound_tag: no profile kernel runs) builds them here on first use.
     DevBuf d_text2;
     uint32_t text2_stride = 0;
     bool text2_ready = false;
-    bool ensure_text2()
+    bool filter_wanted() const { return !variant("nn_no_block_filter") && !variant("nn_no_list") && st->maxlen < 16384; }          // (what plan_lists asks in front of the filter)
+    bool text2_room()
     {
-        if (text2_ready) return true;
+        if (d_text2.p) return true;
         text2_stride = nnf_text2_stride(st->maxlen);
         size_t free_b = 0;
         if (!free_mem(free_b) || (size_t)n * text2_stride * 4 > free_b / 2 + st->pool.slots[SLOT_NN_TEXT2].cap) return false;
         d_text2.pool = &st->pool;
         d_text2.slot = SLOT_NN_TEXT2;
-        if (d_text2.alloc((size_t)std::max<uint32_t>(n, 1) * text2_stride * 4) != ISOCON_OK) return false;
+        if (d_text2.alloc((size_t)std::max<uint32_t>(n, 1) * text2_stride * 4) != ISOCON_OK) { d_text2.p = nullptr; return false; }
+        return true;
+    }
+    bool ensure_text2()
+    {
+        if (text2_ready) return true;
+        if (!text2_room()) return false;
         hipLaunchKernelGGL(k_build_text2, dim3(std::max<uint32_t>(n, 1)), dim3(256), 0, 0, st->dev, d_text2.as<uint32_t>(), text2_stride);
         if (hipGetLastError() != hipSuccess) return false;
         text2_ready = true;
@@ -185,6 +196,21 @@ struct NNContext {
         ISO_HIP_CHECK(hipMemsetAsync(d_hit_count.p, 0, 8, 0));
         ISO_HIP_CHECK(hipMemsetAsync(d_stats.p, 0, N_COUNTERS * 8, 0));
         return ISOCON_OK;
+    }
+    // Start of a pass of the 64-row phase: bounds, role flags (if nn_setup left them to this point) and counters.  The ordinary step --
+    // constant roles, best[] a fill -- does all of it in one launch (k_nn_step_init) instead of five fills.
+    int begin_pass()
+    {
+        if (flags_deferred && fill_best && n) {
+            flags_deferred = fill_best = false;
+            hipLaunchKernelGGL(k_nn_step_init, dim3((std::max<uint32_t>(n, N_COUNTERS) + 255) / 256), dim3(256), 0, 0, d_best.as<int32_t>(), d_qf.as<uint8_t>(), d_tf.as<uint8_t>(), n,
+                               (int32_t)NN_INF, d_hit_count.as<unsigned long long>(), d_stats.as<unsigned long long>(), N_COUNTERS);
+            ISO_HIP_CHECK(hipGetLastError());
+            return ISOCON_OK;
+        }
+        int rc;
+        if ((rc = flush_flags()) || (rc = upload_best())) return rc;
+        return reset_counters();
     }
     void add_counters(const unsigned long long *sc2)
     {
@@ -288,10 +314,23 @@ struct NNContext {
     bool dev_excluded(uint32_t q) const { return mask_exc && is_exc(q); }
     bool flags_dirty = false;      // a wide stage left its own query flags on the device
     bool roles_uniform = false;    // 1-set, no is_converged: every entry is query and target
+    // isocon_nn_graph: constant role flags are not filled by nn_setup but with the start of the first pass (begin_pass), or by
+    // flush_flags() in front of anything else that reads them on the device
+    bool defer_flags = false, flags_deferred = false;
+    int flush_flags()
+    {
+        if (!flags_deferred) return ISOCON_OK;
+        flags_deferred = false;
+        ISO_HIP_CHECK(hipMemsetAsync(d_qf.p, 1, n, 0));
+        ISO_HIP_CHECK(hipMemsetAsync(d_tf.p, 1, n, 0));
+        return ISOCON_OK;
+    }
     int upload_flags(bool fresh = false)
     {
         if (!n) return ISOCON_OK;
+        flags_deferred = false;          // (whatever follows writes both arrays)
         if (fresh && roles_uniform && !st->n_exc) {          // (nn_setup: nothing to send, both role arrays are constants)
+            if (defer_flags) { flags_deferred = true; return ISOCON_OK; }
             ISO_HIP_CHECK(hipMemsetAsync(d_qf.p, 1, n, 0));
             ISO_HIP_CHECK(hipMemsetAsync(d_tf.p, 1, n, 0));
             return ISOCON_OK;

@@ -228,12 +228,13 @@ extern "C" int isocon_nn_graph(isocon_store *s, const uint8_t *is_converged, con
                    ~Total() { if (getenv("ISOCON_DEBUG")) fprintf(stderr, "[isocon] %-28s %8.2f ms\n", "isocon_nn_graph total", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count()); } } total;
     WaitScope waits(s);
     NNContext C;
+    C.defer_flags = true;          // (constant role flags: filled with the start of the first pass, NNContext::begin_pass)
     int rc = nn_setup(C, s, is_converged, is_target, depth, nullptr, true);
     if (rc) return rc;
     clk0.lap("setup");
     if (getenv("ISOCON_DEBUG")) { (void)hipDeviceSynchronize(); clk0.lap("sync after setup"); }
     // 2-set with a depth limit that binds: the order-dependent rule of NNG:416, round by round (ISOCON_DEBUG_VARIANT=nn_2set_walk: every 2-set call)
-    if (C.two_set && (C.depth_binds || variant("nn_2set_walk"))) return nn2_depth_graph(C, depth, out_best, out_row_ptr, out_cols, cols_cap, n_cols_needed, stats);
+    if (C.two_set && (C.depth_binds || variant("nn_2set_walk"))) return (rc = C.flush_flags()) ? rc : nn2_depth_graph(C, depth, out_best, out_row_ptr, out_cols, cols_cap, n_cols_needed, stats);
     C.keep_dev = n >= 1024 && !variant("nn_host_finalize");
     C.csr_follows = C.keep_dev;          // the ordinary case ends the 64-row phase with one record: hits and bounds stay on the device for the CSR kernels
     C.fill_best = !s->n_exc;             // no bounds from the caller: best[] starts as a fill on the device

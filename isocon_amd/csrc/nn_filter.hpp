@@ -15,7 +15,11 @@
 // a hit of either end and leaves the list.  (The maximum over all shifted tilings of disjoint blocks is the same idea without the
 // restart behind every error; it rejects 84 % where greedy rejects 99 %.)
 //
-//   k_build_text2        2-bit texts: row i = the bases of sequence i, 16 per dword (base j at bits 2j, 2j + 1 of dword j / 16), zero padded
+//   the 2-bit texts      row i = the bases of sequence i, 16 per dword (base j at bits 2j, 2j + 1 of dword j / 16), zero padded up to
+//                        nnf_text2_stride (text2_word, common.hpp).  In a step they are written by the profile kernel of the q-gram bound
+//                        (k_qgram_profile4, qgram_mm.hpp), which walks every sequence's planes anyway; k_build_text2 writes the same rows
+//                        for the entries that run the filter without a profile kernel in front (isocon_block_bound_pairs,
+//                        isocon_block_filter_chunks, a main phase that finds its bound matrix in the pool)
 //   k_nn_block_filter    one workgroup per chunk of the list builder (nn_list.hpp): the owner's 8-gram set as a bitmap in LDS (bit set =
 //                        ABSENT), one partner per lane streaming its text in 64-byte pieces, four probes per dword (b = 8, s = 4);
 //                        survivors are compacted in LDS and leave as a chunk of the same class (enough of them AND less than half of
@@ -50,31 +54,13 @@ __host__ __device__ __forceinline__ uint32_t nnf_text2_stride(int32_t maxlen)
     return ((dw + NNF_BATCH - 1) / NNF_BATCH + 1u) * NNF_BATCH + 4u;
 }
 
-__device__ __forceinline__ uint32_t nnf_spread16(uint32_t x)
-{
-    x = (x | (x << 8)) & 0x00ff00ffu;
-    x = (x | (x << 4)) & 0x0f0f0f0fu;
-    x = (x | (x << 2)) & 0x33333333u;
-    x = (x | (x << 1)) & 0x55555555u;
-    return x;
-}
-
 __global__ __launch_bounds__(256) void k_build_text2(DevStore S, uint32_t *__restrict__ text, uint32_t stride)
 {
     const uint32_t i = blockIdx.x;
     if (i >= S.n) return;
     const int32_t len = S.lens[i];
     uint32_t *row = text + (size_t)i * stride;
-    for (uint32_t j = threadIdx.x; j < stride; j += 256) {
-        uint32_t v = 0;
-        const int32_t c0 = (int32_t)j * 16;
-        if (c0 < len) {
-            const size_t at = ((size_t)(c0 >> 6) * S.n + i) * 2;
-            const uint32_t lo = (uint32_t)(S.planes[at] >> (c0 & 63)) & 0xffffu, hi = (uint32_t)(S.planes[at + 1] >> (c0 & 63)) & 0xffffu;
-            v = nnf_spread16(lo) | (nnf_spread16(hi) << 1);          // (bases past the end are 0 in the planes)
-        }
-        row[j] = v;
-    }
+    for (uint32_t j = threadIdx.x; j < stride; j += 256) row[j] = text2_word(S, i, len, j);
 }
 
 __device__ __forceinline__ unsigned long long nnf_uniform64(unsigned long long v)

@@ -80,6 +80,17 @@ __global__ __launch_bounds__(256) void k_fin_pack(uint32_t n, const unsigned lon
     if (best_out != nullptr && i < n) best_out[i] = best[i];
 }
 
+// The start of a step whose inputs are constants (1-set, every entry query and target, no bounds from the caller), in one launch
+// instead of five fills: best[] = `inf`, both role flags 1, the hit count and the n_stats counters 0.
+__global__ __launch_bounds__(256) void k_nn_step_init(int32_t *__restrict__ best, uint8_t *__restrict__ qflag, uint8_t *__restrict__ tflag, uint32_t n, int32_t inf,
+                                                       unsigned long long *__restrict__ hit_count, unsigned long long *__restrict__ stats, uint32_t n_stats)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) { best[i] = inf; qflag[i] = 1; tflag[i] = 1; }
+    if (i < n_stats) stats[i] = 0;
+    if (i == 0) *hit_count = 0;
+}
+
 // What the host needs of the 64-row phase before the CSR kernels, as one record: rec[0] = hits recorded, rec[1] = 1 if an entry that acts
 // as a query is still without a neighbour and longer than 63 (the wide-band phase has to run), rec[2 ..] = the n_stats counters.
 // rec[1] is zero at launch.

@@ -37,7 +37,7 @@ int NNContext::plan_lists(const QMap &Q, uint32_t nq, const NNParams &PR, ListPl
     L.sorted_b = L.sorted_a + cap_out;
     ISO_HIP_CHECK(hipMemsetAsync(d_ltot.p, 0, sizeof(NNPlanTotals), 0));
     NNBoundRows B;
-    B.lb = PR.lb; B.row_off = PR.lb_row; B.row_len = static_cast<const uint32_t *>(st->pool.slots[SLOT_NN_LBLEN].p);
+    B.lb = PR.lb; B.row_off = PR.lb_row; B.row_len = lb_len_dev;
     B.lbT = static_cast<const uint8_t *>(st->pool.slots[SLOT_NN_LBT].p);
     B.offT = static_cast<const unsigned long long *>(st->pool.slots[SLOT_NN_LBT_OFF].p);
     B.sloT = static_cast<const uint32_t *>(st->pool.slots[SLOT_NN_LBT_SLO].p);

@@ -387,7 +387,7 @@ int nn_phase_a_planes(NNContext &C, const QMap &Q, bool allow_regroup = false,
     const bool whole_set = Q.begin == 0 && Q.end == n && Q.stride == 1 && Q.block_log2 == 0 && C.depth >= n;
     for (;;) {
         int rc;
-        if ((rc = C.upload_best()) || (rc = C.reset_counters())) return rc;
+        if ((rc = C.begin_pass())) return rc;
         clk.lap("phaseA: upload/reset");
         PhaseAPass P(do_seed, do_main, seeded_before);
         if (!C.two_set || two_set_lists) {

@@ -83,9 +83,20 @@ __device__ __forceinline__ uint32_t qg_spread8(uint32_t x)
 // psum[i] = sum of the stored vector.  One workgroup per QP_SEQS consecutive sequences: presence bitset + excess counters in LDS, one
 // sequence after the other; the rows of a K-block are adjacent in memory, so the workgroup's QP_SEQS rows leave as pieces of
 // QP_SEQS x 64 contiguous bytes (one sequence per workgroup wrote 64-byte pieces: half a cache line each, 0.50 ms at C3; four: 0.3x ms).
-static constexpr int QP_SEQS = 4;
+// Wider pieces do not pay (profiles/step_front_ab.txt, C3, kernel time with the text rows / step): QP_SEQS 4: 218 us / 7.43 ms, 8: 255 us /
+// 7.49 ms, 16: 395 us / 7.60 ms -- a workgroup handles its sequences one after the other, so more of them per workgroup means fewer
+// workgroups to hide the gram loop's LDS atomics behind, and at 4 the kernel already writes 2.0 TB/s.
+// text2 != nullptr: the kernel also writes the 2-bit text row of every sequence it profiles (text2_word, common.hpp: text2_stride dwords,
+// zero behind the sequence's end) -- the rows the block filter reads (nn_filter.hpp); the planes it packs are the ones the gram loop
+// reads next.
+#ifndef ISOCON_QP_SEQS                    // (experiments: scripts/dev/build_variant.sh NAME -DISOCON_QP_SEQS=...)
+#define ISOCON_QP_SEQS 4
+#endif
+static constexpr int QP_SEQS = ISOCON_QP_SEQS;
+static_assert(QP_SEQS >= 1 && QP_SEQS <= 16 && (QP_SEQS & (QP_SEQS - 1)) == 0, "QP_SEQS x (2 KB of bitsets) + the excess counters stay below 64 KB of LDS");
 
-__global__ __launch_bounds__(256) void k_qgram_profile4(DevStore S, uint8_t *__restrict__ prof4, uint32_t *__restrict__ psum, uint32_t n_pad)
+__global__ __launch_bounds__(256) void k_qgram_profile4(DevStore S, uint8_t *__restrict__ prof4, uint32_t *__restrict__ psum, uint32_t n_pad,
+                                                        uint32_t *__restrict__ text2, uint32_t text2_stride)
 {
     __shared__ uint32_t bits[QP_SEQS][QM_K / 32];            // presence bits, then QG_CAP level bitsets of the excess bins
     __shared__ uint32_t exh[QG_B1];
@@ -98,8 +109,13 @@ __global__ __launch_bounds__(256) void k_qgram_profile4(DevStore S, uint8_t *__r
     for (uint32_t r = 0; r < cnt; ++r) {
         const uint32_t i = i0 + r;
         for (int e = threadIdx.x; e < QG_B1; e += 256) exh[e] = 0;
+        const int32_t len = S.lens[i];
+        if (text2) {
+            uint32_t *row = text2 + (size_t)i * text2_stride;
+            for (uint32_t j = threadIdx.x; j < text2_stride; j += 256) row[j] = text2_word(S, i, len, j);
+        }
         __syncthreads();
-        const int32_t ngrams = S.lens[i] - QG_Q + 1;
+        const int32_t ngrams = len - QG_Q + 1;
         for (int32_t j = threadIdx.x; j < ngrams; j += 256) {
             const int32_t c = j >> 6, o = j & 63;
             const size_t at = ((size_t)c * S.n + i) * 2;
@@ -130,23 +146,22 @@ __global__ __launch_bounds__(256) void k_qgram_profile4(DevStore S, uint8_t *__r
         }
         __syncthreads();
     }
-    // write: element e = (K-block, sequence, 16-byte slot) in memory order: consecutive threads fill QP_SEQS x 64 contiguous bytes
-    uint32_t local[QP_SEQS];
-#pragma unroll
-    for (int r = 0; r < QP_SEQS; ++r) local[r] = 0;
+    // write: element e = (K-block, sequence, 16-byte slot) in memory order: consecutive threads fill QP_SEQS x 64 contiguous bytes.
+    // A thread's elements are 256 apart, a whole number of K-blocks: they all belong to one sequence r.
+    static_assert(256 % (QP_SEQS * QM_SLOTS) == 0, "a thread's elements of the write loop share their sequence");
+    const int r = (threadIdx.x / QM_SLOTS) % QP_SEQS, sl = threadIdx.x % QM_SLOTS;
+    uint32_t local = 0;
     for (int e = threadIdx.x; e < QP_SEQS * (QM_K / 32); e += 256) {
-        const int kb = e / (QP_SEQS * QM_SLOTS), r = (e / QM_SLOTS) % QP_SEQS, sl = e % QM_SLOTS;
+        const int kb = e / (QP_SEQS * QM_SLOTS);
         const uint32_t w = bits[r][kb * QM_SLOTS + sl];
-#pragma unroll
-        for (int rr = 0; rr < QP_SEQS; ++rr) local[rr] += rr == r ? (uint32_t)__popc(w) : 0u;
+        local += (uint32_t)__popc(w);
         if ((uint32_t)r < cnt) {
             uint4 o;
             o.x = qg_spread8(w & 0xffu); o.y = qg_spread8((w >> 8) & 0xffu); o.z = qg_spread8((w >> 16) & 0xffu); o.w = qg_spread8(w >> 24);
             *reinterpret_cast<uint4 *>(prof4 + ((size_t)kb * n_pad + i0 + (uint32_t)r) * QM_ROWB + (size_t)sl * 16) = o;
         }
     }
-#pragma unroll
-    for (int r = 0; r < QP_SEQS; ++r) if (local[r]) atomicAdd(&s_sum[r], local[r]);
+    if (local) atomicAdd(&s_sum[r], local);
     __syncthreads();
     if (threadIdx.x < cnt) psum[i0 + threadIdx.x] = s_sum[threadIdx.x];
 }
@@ -584,6 +599,18 @@ __global__ __launch_bounds__(512, 2) void k_qgram_mm(const uint8_t *__restrict__
         g_qm_timeline[blockIdx.x * 8u + 6] = hw;
     }
 #endif
+}
+
+// The fills in front of k_qgram_mm in one launch (hub scores, row / column minima, the seed arrays and their counter: six fills cost the
+// host 50 us of enqueueing on the path that bounds the start of k_qgram_mm): range r = `words` dwords of `value`; unused ranges have 0 words.
+struct QMFillRange { uint32_t *p; unsigned long long words; uint32_t value; };
+struct QMFills { QMFillRange r[6]; };
+__global__ __launch_bounds__(256) void k_qm_fills(QMFills F)
+{
+    const unsigned long long first = (unsigned long long)blockIdx.x * 256u + threadIdx.x, step = (unsigned long long)gridDim.x * 256u;
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+        for (unsigned long long i = first; i < F.r[k].words; i += step) F.r[k].p[i] = F.r[k].value;
 }
 
 // Row layout of the transposed matrix (nn_bounds.inc, build_bounds): for entry p the launch slots whose window holds p -- the slots s with
