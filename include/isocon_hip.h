@@ -407,11 +407,15 @@ int isocon_hw_pairs_wide(isocon_store *s, const uint32_t *q, const uint32_t *t, 
  * adjacent ops differ, none empty.  Which optimal path is reported is the oracle's tie rule (from the end cell: 'I', then 'D', then the
  * diagonal; oracle/isocon_oracle.c orc_nw_path).  ISOCON_E_CAPACITY + *needed when ops_cap is too small (out_ed and out_ops_ptr are
  * valid then).
- * The distances come first, through the implementation of isocon_ed_pairs; only the pairs within their threshold are traced, by
- * un-banded kernels (one wavefront per pair, the whole query in 64-row blocks against the whole target, 16 bytes of trace per block
- * and column: about len_q * len_t / 4 bytes).  The traces of one launch stay within 1 GiB of scratch: the list is cut into as many
- * launches as that takes, and a single pair that needs more on its own is refused with ISOCON_E_UNSUPPORTED (isocon_last_error states
- * its sizes).  So is a query of more than 4 096 bases against a target of more than 655 360.  A pair with an empty sequence is answered
+ * The distances come first, through the implementation of isocon_ed_pairs; only the pairs within their threshold are traced.  A path
+ * of distance ed stays on at most ed + 1 diagonals (the corridor: |d| + 2 ((ed - |d|) / 2) + 1 of them, d = len_q - len_t).  A hit whose
+ * corridor is at most 256 diagonals is traced by the banded kernels: one lane per pair, a window of 64, 128 or 256 rows that slides
+ * along the corridor, 16 bytes of trace per column and 64 window rows -- 16 * len_t bytes at up to 64 diagonals, whatever len_q is.
+ * Any other hit is traced by the un-banded kernel (one wavefront per pair, the whole query in 64-row blocks against the whole target,
+ * 16 bytes of trace per block and column: about len_q * len_t / 4 bytes).  The traces of one launch of either kind stay within 1 GiB
+ * of scratch: the list is cut into as many launches as that takes, and a single pair that needs more on its own is refused with
+ * ISOCON_E_UNSUPPORTED (isocon_last_error states its sizes).  So is, among the hits of more than 256 diagonals only, a query of more
+ * than 4 096 bases against a target of more than 655 360.  A pair with an empty sequence is answered
  * on the host (one 'D' or one 'I' op; none when both are empty).  A store under its own map of at most four symbols works unchanged
  * (only equality matters); one with more than four symbols returns ISOCON_E_ALPHABET; ids out of range ISOCON_E_ARG.
  * *kernel_ms sums the distance and the path kernels.
@@ -429,14 +433,27 @@ int isocon_ed_path_pairs(isocon_store *s, const uint32_t *q, const uint32_t *t, 
  * oracle's tie rule (from the end cell: 'I', then 'D', then the diagonal; oracle.hw_path).  A pair above its threshold has no ops.
  * ISOCON_E_CAPACITY + *needed when ops_cap is too small (out and out_ops_ptr are valid then).
  * Two stages: the rows come through the implementation of isocon_hw_pairs_wide (banded kernels where the band fits), then every hit is
- * traced over its window alone by the un-banded kernel of isocon_ed_path_pairs (16 bytes of trace per 64-row block and window column;
- * the target outside the window is not stored).  The traces of one launch stay within 1 GiB of scratch: the hits are cut into as many
- * launches as that takes, and a pair that needs more on its own is refused with ISOCON_E_UNSUPPORTED (isocon_last_error states its
- * sizes).  So is a query of more than 4 096 bases against a window of more than 655 360.  *kernel_ms sums both stages.
+ * traced over its window alone by the kernels of isocon_ed_path_pairs: the banded ones where the corridor of (query, window, distance)
+ * is at most 256 diagonals (16 bytes of trace per window column and 64 window rows), else the un-banded one (16 bytes per 64-row block
+ * and window column); the target outside the window is not stored.  The traces of one launch stay within 1 GiB of scratch: the hits are
+ * cut into as many launches as that takes, and a pair that needs more on its own is refused with ISOCON_E_UNSUPPORTED (isocon_last_error
+ * states its sizes).  So is, among the hits of more than 256 diagonals only, a query of more than 4 096 bases against a window of more
+ * than 655 360.  *kernel_ms sums both stages.
  */
 int isocon_hw_path_pairs(isocon_store *s, const uint32_t *q, const uint32_t *t, const int32_t *k, uint64_t n_pairs,
                          int32_t *out /* n_pairs x 5 */, uint32_t *out_ops, uint64_t *out_ops_ptr, uint64_t ops_cap,
                          uint64_t *needed, float *kernel_ms);
+
+/*
+ * How the calling thread's last isocon_ed_path_pairs / isocon_hw_path_pairs call traced its hits (no counterpart in the reference).
+ * out[0] hits traced; out[1..3] hits of the banded classes of 1, 2 and 4 window words (64, 128, 256 diagonals); out[4] hits of the
+ * un-banded kernel; out[5] / out[6] bytes of trace banded / un-banded; out[7] / out[8] launches banded / un-banded; out[9] / out[10]
+ * kernel milliseconds of the banded trace + walk / the un-banded one; out[11] of the forward-op kernel.  Either entry zeroes the values
+ * when it is called: a call without pairs or hits, and one that fails before its hits are classed or refuses one of them
+ * (ISOCON_E_ARG, ISOCON_E_ALPHABET, a failure of the distance or row stage, ISOCON_E_UNSUPPORTED), reports zeros; one that fails later
+ * (ISOCON_E_CAPACITY) reports what it had done.  Writes min(cap, 12) values and returns that number.
+ */
+int isocon_path_last_stats(double *out, int32_t cap);
 
 /*
  * Device read tables of the hypothesis test: which reads support a candidate against its reference, and every read's error counts,

@@ -5,6 +5,7 @@
 extern "C" int isocon_hw_path_pairs(isocon_store *s, const uint32_t *q, const uint32_t *t, const int32_t *k, uint64_t n_pairs,
                                     int32_t *out, uint32_t *out_ops, uint64_t *out_ops_ptr, uint64_t ops_cap, uint64_t *needed, float *kernel_ms)
 {
+    path_stats_reset();
     if (!s || !out_ops_ptr || (n_pairs && (!q || !t || !k || !out)) || (ops_cap && !out_ops)) return ISOCON_E_ARG;
     if (kernel_ms) *kernel_ms = 0.f;
     if (needed) *needed = 0;

@@ -28,6 +28,7 @@
 #include "hw_tiles.hpp"
 #include "hw_full.hpp"
 #include "nw_path.hpp"
+#include "nw_band.hpp"
 #include "ed_lanes.hpp"
 #include "ed_bytes.hpp"
 #include "nn2_depth.hpp"
@@ -102,7 +103,7 @@ struct HeldHits { uint64_t store_serial = 0; uint64_t rows = 0; };
 // hipMalloc/hipFree (tens of ms for the multi-GB trace scratch) every time.
 struct ScratchPool {
     struct Slot { void *p = nullptr; size_t cap = 0; };
-    Slot slots[160];
+    Slot slots[168];
     BoundTag bound_tag;
     HeldHits held_hits;
     MsaBuilt msa;
@@ -141,9 +142,10 @@ enum {
     SLOT_EV_IN, SLOT_EV_OUT, SLOT_EV_SNIP,
     SLOT_PB_IN, SLOT_PB_OUT,
     SLOT_NWP_Q, SLOT_NWP_T, SLOT_NWP_ED, SLOT_NWP_TOFF, SLOT_NWP_ROFF, SLOT_NWP_REV, SLOT_NWP_RUNS, SLOT_NWP_FOFF, SLOT_NWP_OPS, SLOT_NWP_START, SLOT_NWP_COLS,
+    SLOT_NWB_TRACE, SLOT_NWB_SLOTS, SLOT_NWB_WOFF, SLOT_NWB_WCOLS, SLOT_NWB_WLANES,
     SLOT_COUNT
 };
-static_assert(SLOT_COUNT <= 160, "ScratchPool::slots too small");
+static_assert(SLOT_COUNT <= 168, "ScratchPool::slots too small");
 
 // One pool per process (one process drives one GPU): scratch outlives the individual stores, because the Python
 // wrappers create a fresh store per call (the reference's functions are stateless).

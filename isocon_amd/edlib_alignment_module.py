@@ -127,8 +127,9 @@ def _cigar_of_steps(steps):
 def edlib_traceback(x, y, mode="NW", task="path", k=1):
     """EAM:130-135: (editDistance, locations, cigar) of edlib.align(x, y, mode="NW", task="path", k=k).  Its only caller
     (isocon_statistical_test.get_nearest_neighbor_graph, :63-104) is never called in v0.3.3.  Distance
-    and path come from the GPU (SeqStore.ed_path_pairs: the k-bounded distance first, the path of a hit from the un-banded
-    trace kernels), with the tie rule used everywhere else (from the end: I, then D, then the diagonal; "parity unpinned");
+    and path come from the GPU (SeqStore.ed_path_pairs: the k-bounded distance first, the path of a hit from the trace
+    kernels: banded on the diagonals within the distance where those are at most 256, un-banded -- with a trace of about
+    len(x) * len(y) / 4 bytes that must fit 1 GiB -- beyond), with the tie rule used everywhere else (from the end: I, then D, then the diagonal; "parity unpinned");
     above k edlib reports (-1, [], None).  Two cases stay on the host (functions.nw_path_cigar, a full matrix in Python:
     short sequences only): a pair that holds more than four distinct symbols (the path kernels run on the 2-bit planes;
     its distance still comes from the GPU), and a machine without a GPU.  TRACEBACK_STATS counts the calls per route.

@@ -111,7 +111,9 @@ class SeqStore(object):
     def ed_path_pairs(self, q, t, k=None, return_ms=False):
         """edlib.align(q[p], t[p], mode="NW", task="path", k[p]) for a pair list (isocon_ed_path_pairs): (ed int32[n] -- -1 above k --,
         ops uint32[], ops_ptr uint64[n + 1]); pair p owns ops[ops_ptr[p]:ops_ptr[p + 1]], len << 4 | code (0 '=', 1 'X', 2 'I' query
-        only, 3 'D' target only) in forward order.  k: None (unbounded), a scalar or one value per pair (negative: unbounded)."""
+        only, 3 'D' target only) in forward order.  k: None (unbounded), a scalar or one value per pair (negative: unbounded).
+        A hit whose distance keeps its path within 256 diagonals is traced on 16-64 bytes per base of t[p], whatever len(q[p]) is; only
+        beyond that does a pair need about len(q) * len(t) / 4 bytes, which must fit 1 GiB (path_last_stats() tells the routes)."""
         q = np.ascontiguousarray(q, dtype=np.uint32)
         t = np.ascontiguousarray(t, dtype=np.uint32)
         if len(q) != len(t):
@@ -139,7 +141,10 @@ class SeqStore(object):
         hw_pairs(wide=True): distance or -1, start, end, leading / trailing insertion run --, ops uint32[], ops_ptr uint64[n + 1]); a hit
         p owns ops[ops_ptr[p]:ops_ptr[p + 1]], the global alignment of q[p] against t[p][start:end + 1], encoded as in ed_path_pairs.
         k: a scalar or one value per pair; None or a negative value: unbounded (sent as len(q[p]), which an infix distance never
-        exceeds)."""
+        exceeds).  The rows have the limits of hw_pairs(wide=True).  The path of a hit whose distance keeps it within 256 diagonals of
+        (query, located window) is traced on 16-64 bytes per window column, whatever len(q[p]) is; only beyond that does a hit need
+        about len(q) * (end - start + 1) / 4 bytes, which must fit 1 GiB, and is a query of more than 4 096 bases against a window of
+        more than 655 360 refused (path_last_stats() tells the routes of the last call)."""
         q = np.ascontiguousarray(q, dtype=np.uint32)
         t = np.ascontiguousarray(t, dtype=np.uint32)
         if len(q) != len(t):
@@ -484,6 +489,17 @@ def sg_last_stats():
     _lib.load().isocon_sg_last_stats(out, 11)
     keys = ("forward_ms", "walk_ms", "compact_ms", "expand_ms", "pairs_band", "pairs_strips", "pairs_redone", "trace_bytes", "pairs_band_narrow",
             "pairs_tried_narrow", "pairs_retried_wider")
+    return dict(zip(keys, list(out)))
+
+
+def path_last_stats():
+    """how this thread's most recent path call (ed_path_pairs / hw_path_pairs) traced its hits (isocon_path_last_stats, include/isocon_hip.h):
+    hits per class of the banded kernels (W = 1, 2, 4 window words), hits left to the un-banded kernel, bytes of trace, launches and
+    kernel milliseconds of either route and of the forward-op kernel"""
+    out = (ctypes.c_double * 12)()
+    _lib.load().isocon_path_last_stats(out, 12)
+    keys = ("hits", "hits_w1", "hits_w2", "hits_w4", "hits_unbanded", "trace_bytes_band", "trace_bytes_unbanded", "launches_band", "launches_unbanded",
+            "band_ms", "unbanded_ms", "emit_ms")
     return dict(zip(keys, list(out)))
 
 

@@ -1,6 +1,7 @@
 """Global alignment paths of a pair list on the device (SeqStore.ed_path_pairs = isocon_ed_path_pairs, csrc/nw_path.hpp): `pairs`
 related pairs of reads of about `length` bases (two reads of one isoform with i.i.d. errors each: distances of about 20-60).  Median
-of 5 calls after a warm-up: wall and kernel ms, bytes of trace per pair and launches under the 1 GiB budget, and the un-banded
+of 5 calls after a warm-up: wall and kernel ms, the route the hits took (store.path_last_stats: classes of the banded kernels, bytes of
+trace, launches, kernel ms; ISOCON_DEBUG_VARIANT=nwp_unbanded times the un-banded kernel), what the un-banded store would be, and its
 overhead (64-row blocks computed and stored per column against those a trace restricted to the diagonals within ed of the
 corner-to-corner corridor would need).  Beside it: oracle.nw_path (full matrix in C, one core) on a sample of the same list, paths
 compared, and on 3 pairs the host route edlib_traceback took before the device route existed (the distance from isocon_ed_pairs, then
@@ -11,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
 from isocon_amd import synth
-from isocon_amd.store import SeqStore
+from isocon_amd.store import SeqStore, path_last_stats
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--pairs", type=int, default=2000)
@@ -58,6 +59,7 @@ for rep in range(5):
     ed, ops, ops_ptr, ms = st.ed_path_pairs(q, t, return_ms=True)
     walls.append(time.perf_counter() - t0)
     kms.append(ms)
+stats = path_last_stats()
 need = np.array([trace_bytes(int(lens[a]), int(lens[b])) for a, b in zip(q, t)], dtype=np.int64)
 launches, held = 1, 0
 for b in need.tolist():          # the host's cut (nw_path_host.inc): consecutive pairs while their stores fit 1 GiB together
@@ -69,8 +71,12 @@ blocks_full = (m + 63) // 64
 blocks_band = np.minimum(blocks_full, (2 * ed + 1 + np.abs(n - m) + 63) // 64 + 1)
 say("# %s%d pairs of %d .. %d bases (length %d, error rate %.4f per read), distances %d .. %d (median %d), %d ops (%.1f per pair)"
     % (args.label + ": " if args.label else "", args.pairs, lens.min(), lens.max(), args.length, args.rate, ed.min(), ed.max(), int(np.median(ed)), len(ops), len(ops) / args.pairs))
-say("ed_path_pairs: wall median %.1f ms (min %.1f, max %.1f), kernels median %.1f ms; trace %.2f MB per pair (%.2f GB in all), %d launches under the 1 GiB budget"
+say("ed_path_pairs: wall median %.1f ms (min %.1f, max %.1f), kernels median %.1f ms; the un-banded trace would be %.2f MB per pair (%.2f GB in all), %d launches under the 1 GiB budget"
     % (1e3 * float(np.median(walls)), 1e3 * min(walls), 1e3 * max(walls), float(np.median(kms)), need.mean() / 1e6, need.sum() / 1e9, launches))
+say("    route of the hits (store.path_last_stats; ISOCON_DEBUG_VARIANT=%s): W = 1 / 2 / 4: %d / %d / %d, un-banded %d; trace %.3f MB banded + %.3f MB un-banded; launches %d + %d; "
+    "kernels of the last call: banded trace + walk %.2f ms, un-banded %.2f ms, forward ops %.2f ms"
+    % (os.environ.get("ISOCON_DEBUG_VARIANT", ""), stats["hits_w1"], stats["hits_w2"], stats["hits_w4"], stats["hits_unbanded"], stats["trace_bytes_band"] / 1e6,
+       stats["trace_bytes_unbanded"] / 1e6, stats["launches_band"], stats["launches_unbanded"], stats["band_ms"], stats["unbanded_ms"], stats["emit_ms"]))
 say("    un-banded overhead: %.1f blocks of 64 rows per column computed and stored, %.1f would hold the diagonals within ed of the corridor: factor %.1f"
     % (blocks_full.mean(), blocks_band.mean(), float((blocks_full / blocks_band).mean())))
 if args.oracle_sample:

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
 from isocon_amd import synth
-from isocon_amd.store import SeqStore
+from isocon_amd.store import SeqStore, path_last_stats
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--pairs", type=int, default=2000)
@@ -68,6 +68,7 @@ st.hw_path_pairs(q[:64], t[:64], args.k)          # warm-up
 st.hw_path_pairs(q[:64], t[:64])
 st.ed_path_pairs(q[:64], t[:64])
 (rows, ops, ops_ptr, _), path_k = median5(lambda: st.hw_path_pairs(q, t, args.k, return_ms=True))
+stats_k = path_last_stats()
 (rows_u, ops_u, ops_ptr_u, _), path_u = median5(lambda: st.hw_path_pairs(q, t, return_ms=True))
 (loc, _), loc_k = median5(lambda: st.hw_pairs(q, t, args.k, return_ms=True, wide=True))
 (loc_u, _), loc_un = median5(lambda: st.hw_pairs(q, t, lens[q].astype(np.int32), return_ms=True, wide=True))
@@ -77,9 +78,13 @@ need = np.array([trace_bytes(int(m), int(c)) for m, c in zip(lens[q][hit], cols)
 whole = np.array([trace_bytes(int(m), int(n)) for m, n in zip(lens[q][hit], lens[t][hit])], dtype=np.int64)
 say("# %s%d pairs: queries of %d .. %d bases inside targets of %d .. %d (length %d, error rate %.4f per read, 20-100 bases trimmed from either end of the query)"
     % (args.label + ": " if args.label else "", args.pairs, lens[q].min(), lens[q].max(), lens[t].min(), lens[t].max(), args.length, args.rate))
-say("hw_path_pairs, k = %d (%d hits, distances %d .. %d, median %d): %s; %d ops (%.1f per hit); trace %.2f MB per hit (%.2f GB in all; the whole target would be %.2f GB)"
+say("hw_path_pairs, k = %d (%d hits, distances %d .. %d, median %d): %s; %d ops (%.1f per hit); the un-banded trace would be %.2f MB per hit (%.2f GB in all; the whole target %.2f GB)"
     % (args.k, int(hit.sum()), rows[hit, 0].min() if hit.any() else -1, rows[hit, 0].max() if hit.any() else -1, int(np.median(rows[hit, 0])) if hit.any() else -1, path_k,
        len(ops), len(ops) / max(int(hit.sum()), 1), need.mean() / 1e6 if hit.any() else 0.0, need.sum() / 1e9, whole.sum() / 1e9))
+say("    route of the hits (store.path_last_stats; ISOCON_DEBUG_VARIANT=%s): W = 1 / 2 / 4: %d / %d / %d, un-banded %d; trace %.3f MB banded + %.3f MB un-banded; launches %d + %d; "
+    "kernels of the last call: banded trace + walk %.2f ms, un-banded %.2f ms, forward ops %.2f ms"
+    % (os.environ.get("ISOCON_DEBUG_VARIANT", ""), stats_k["hits_w1"], stats_k["hits_w2"], stats_k["hits_w4"], stats_k["hits_unbanded"], stats_k["trace_bytes_band"] / 1e6,
+       stats_k["trace_bytes_unbanded"] / 1e6, stats_k["launches_band"], stats_k["launches_unbanded"], stats_k["band_ms"], stats_k["unbanded_ms"], stats_k["emit_ms"]))
 say("    hw_pairs(wide=True) alone, k = %d: %s; rows equal: %s" % (args.k, loc_k, bool((loc == rows).all())))
 say("hw_path_pairs, unbounded (k = len(q): the un-banded locate): %s; %d hits, %d ops; same paths as under k = %d for its hits: %s"
     % (path_u, int((rows_u[:, 0] >= 0).sum()), len(ops_u), args.k,
