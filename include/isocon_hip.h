@@ -183,6 +183,8 @@ typedef struct {
     uint64_t pairs_block_rejected;/* survivors of the q-gram bound that the block filter rejected (greedy count of disjoint absent 8-grams > threshold; never aligned) */
     float filter_kernel_ms;       /* HIP-event time of the block filter (part of list_kernel_ms) */
     float mm_kernel_ms;           /* ... of the bound matrix contraction k_qgram_mm alone (part of bound_kernel_ms) */
+    uint64_t pairs_seed_known;    /* of pairs_lanes: pairs the seed pass of the same call had aligned already (their outcome is final: not aligned again, unless ISOCON_DEBUG_VARIANT=nn_seed_skip=0 / =count) */
+    uint64_t pairs_lanes_aligned; /* pairs the one-pair-per-lane launch of the main pass ran: pairs_lanes - pairs_seed_known (pairs_lanes with nn_seed_skip=0 / =count) */
 } isocon_nn_stats;
 
 /*

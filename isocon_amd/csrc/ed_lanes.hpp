@@ -19,10 +19,14 @@ namespace isocon {
 //   NN == false: out[i] = distance if <= pk[i] (0 <= pk[i] <= 63), else -1.
 //   NN == true : the pair goes through the update rule of the nearest-neighbour search (roles, min_d, best[] by atomicMin,
 //                hit list) with k = min(63, max of the two ends' current bounds), exactly like nn_process_tile.
+// live (nullptr: none): the number of pairs as the device knows it, where the host only has an upper bound to size the launch with
+// (n_pairs); the waves behind it find no pair and leave at the first look at their lanes.
 template <bool NN>
 __global__ __launch_bounds__(256) void k_ed_lanes(DevStore S, NNParams P, const uint32_t *__restrict__ pa, const uint32_t *__restrict__ pb,
-                                                   const int32_t *__restrict__ pk, uint64_t n_pairs, int32_t *__restrict__ out)
+                                                   const int32_t *__restrict__ pk, uint64_t n_pairs, int32_t *__restrict__ out,
+                                                   const unsigned long long *__restrict__ live = nullptr)
 {
+    if (live != nullptr) { const uint64_t nl = *live; n_pairs = nl < n_pairs ? nl : n_pairs; }
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     uint32_t x = 0, y = 0;
     bool valid = i < n_pairs;

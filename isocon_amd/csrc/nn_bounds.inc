@@ -49,7 +49,7 @@ int NNContext::build_bounds(const QMap &Q, int32_t kcap, NNParams &P, bool want_
     struct StopTimer { NNContext &c; bool armed = true; ~StopTimer() { if (armed) c.tm.stop_later(&c.stats.bound_kernel_ms); } } stop_timer{*this};
     // Everything between the profile kernel and k_qgram_mm that neither of them writes or reads goes on the side stream while the
     // profile kernel runs.  At once, while the host lays out the rows: the fills that are sized from n alone -- the hub scores, the
-    // row / column minima, the seed arrays of run_bound_seeds and their counter.  Behind the host's loops: row lengths, tile table and
+    // row / column minima, the seed arrays of run_bound_seeds, their counter and the table of the seed pairs.  Behind the host's loops: row lengths, tile table and
     // row offsets (staged in pinned memory) and the transposed matrix' row layout (k_lbt_rows, its scan, k_lbt_offsets).  The null
     // stream waits for all of it once, in front of k_qgram_mm; the host does not wait at all.  Without a side stream the same
     // operations go on the null stream, the uploads as three blocking copies.
@@ -78,6 +78,12 @@ int NNContext::build_bounds(const QMap &Q, int32_t kcap, NNParams &P, bool want_
             fills.r[3] = {d_seed_a.as<uint32_t>(), n_seed_words, 0xffffffffu};
             fills.r[4] = {d_seed_b.as<uint32_t>(), n_seed_words, 0xffffffffu};
             fills.r[5] = {d_seed_n.as<uint32_t>(), 2, 0u};
+            // the table of the seed pairs (NNSeedKnown): "none" everywhere; no room for it: the seeds run without, the main pass aligns every pair
+            static_assert(NN_KNOWN_SLOTS == 2 * QM_SEEDS, "a table row holds every pair a thread of k_qgram_seed_pairs can propose");
+            d_known.pool = &st->pool;
+            d_known.slot = SLOT_NN_SEED_KNOWN;
+            if (d_known.alloc((size_t)n * NN_KNOWN_SLOTS * 4) == ISOCON_OK) fills.r[6] = {d_known.as<uint32_t>(), (unsigned long long)n * NN_KNOWN_SLOTS, 0xffffffffu};
+            else d_known.p = nullptr;
             rowmin = d_rowmin.as<unsigned long long>();
             colmin = d_colmin.as<unsigned long long>();
         }
@@ -265,12 +271,13 @@ int NNContext::run_bound_seeds(const QMap &Q)
     if (const char *e = variant_value("nn_seed_classes")) { const int v = atoi(e); if (v == 1 || v == 2 || v == QM_SEEDS) col_classes = (uint32_t)v; }      // A/B runs
     // (build_bounds filled the seed arrays and zeroed their counter on its way: seeds_ready says so)
     hipLaunchKernelGGL(k_qgram_seed_pairs, dim3((n + 255) / 256), dim3(256), 0, 0, d_rowmin.as<unsigned long long>(), d_colmin.as<unsigned long long>(),
-                       n, Q, seed_nq, col_classes, d_seed_a.as<uint32_t>(), d_seed_b.as<uint32_t>(), d_seed_n.as<unsigned long long>());
+                       n, Q, seed_nq, col_classes, d_seed_a.as<uint32_t>(), d_seed_b.as<uint32_t>(), d_seed_n.as<unsigned long long>(), d_known.as<uint32_t>());
     ISO_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(k_ed_lanes<true>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, 0, st->dev, params(63), d_seed_a.as<uint32_t>(), d_seed_b.as<uint32_t>(),
                        (const int32_t *)nullptr, np, (int32_t *)nullptr);
     ISO_HIP_CHECK(hipGetLastError());
     tm.stop_later(&stats.seed_kernel_ms);
+    known_ready = d_known.p != nullptr;          // (every pair in the table is in the launch above)
     return ISOCON_OK;
 }
 

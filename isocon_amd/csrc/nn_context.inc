@@ -137,6 +137,22 @@ struct NNContext {
     bool seeds_ready = false;
     uint32_t seed_nq = 0;
     int run_bound_seeds(const QMap &Q);          // nn_bounds.inc
+    // The table of the seed pairs (NNSeedKnown, nn_list.hpp): known_ready from the launch of THIS pass' seed pairs (run_bound_seeds) to the
+    // next start of a pass (begin_pass: best[] is uploaded again, the hit list starts over) -- never across calls.  The kernels that make
+    // flat pairs get it only where its argument holds as it is written down: one set with every entry query and target, thresholds that
+    // tighten, the sequences themselves (not their images).
+    DevBuf d_known;
+    bool known_ready = false;
+    static int seed_skip_mode()          // 1: settled pairs are not aligned again; 0: they are only counted (nn_seed_skip=0 / =count: A/B runs, tests)
+    {
+        const char *e = variant_value("nn_seed_skip");
+        return e && (!strcmp(e, "0") || !strcmp(e, "count")) ? 0 : 1;
+    }
+    NNSeedKnown seed_known() const
+    {
+        if (!known_ready || !roles_uniform || fixed || image_pass || st->n_exc) return NNSeedKnown{nullptr, 0u};
+        return NNSeedKnown{static_cast<const uint32_t *>(d_known.p), (uint32_t)seed_skip_mode()};
+    }
     // The survivors of the bounds as lists (nn_list.hpp).  listed = false when the lists are not affordable or the bounds reject too
     // little (the caller then launches the kernel with its own admission).
     DevBuf d_ltot, d_lchunks, d_list, d_lpa, d_lpb, d_lmeta, d_ltasks;
@@ -145,6 +161,8 @@ struct NNContext {
     struct ListPlan {
         bool listed = false;
         unsigned long long n_chunks = 0, n_chunks_narrow = 0, n_small = 0;
+        unsigned long long seed_known = 0;          // settled pairs the list builder and the filter met (left out of the n_small flat pairs if `K.drop`)
+        NNSeedKnown K = {nullptr, 0u};              // what the kernels of the plan got; k_nn_chunks_to_pairs gets the same
         unsigned long long conv_a = 0, conv_b = 0, conv_pairs = 0;          // chunks (per class) whose pairs the caller appends to the n_small flat pairs
         NNChunk *a = nullptr, *b = nullptr, *sorted_a = nullptr, *sorted_b = nullptr;
     };
@@ -189,8 +207,10 @@ struct NNContext {
         return ISOCON_OK;
     }
     int download_best() { ISO_HIP_CHECK(copy_d2h(best.data(), d_best.p, (size_t)n * 4)); best_on_host = true; return ISOCON_OK; }
-    // d_stats: two counter blocks -- [0] every launch but the 32-row table launch, [1] that one (nn_phase_a)
-    static constexpr uint32_t N_COUNTERS = 2 * (NN_COUNTER_SLOTS * 4 + 1);
+    // d_stats: two counter blocks -- [0] every launch but the 32-row table launch, [1] that one (nn_phase_a) -- and behind them the settled
+    // pairs that k_nn_chunks_to_pairs met (nn_filter.hpp)
+    static constexpr uint32_t KNOWN_COUNTER = 2 * (NN_COUNTER_SLOTS * 4 + 1);
+    static constexpr uint32_t N_COUNTERS = KNOWN_COUNTER + 1;
     int reset_counters()
     {
         ISO_HIP_CHECK(hipMemsetAsync(d_hit_count.p, 0, 8, 0));
@@ -201,6 +221,7 @@ struct NNContext {
     // constant roles, best[] a fill -- does all of it in one launch (k_nn_step_init) instead of five fills.
     int begin_pass()
     {
+        known_ready = false;
         if (flags_deferred && fill_best && n) {
             flags_deferred = fill_best = false;
             hipLaunchKernelGGL(k_nn_step_init, dim3((std::max<uint32_t>(n, N_COUNTERS) + 255) / 256), dim3(256), 0, 0, d_best.as<int32_t>(), d_qf.as<uint8_t>(), d_tf.as<uint8_t>(), n,
@@ -225,6 +246,8 @@ struct NNContext {
                 if (blk == 1) stats.narrow_columns += sc[i * 4 + 1];
             }
         }
+        stats.pairs_seed_known += sc2[KNOWN_COUNTER];
+        if (seed_skip_mode()) stats.pairs_lanes_aligned -= sc2[KNOWN_COUNTER];          // (run_listed_pass counted them as aligned: it only had the upper bound)
     }
     // pulls device hits into `out`; returns ISOCON_E_CAPACITY if the device list overflowed.  filter: drop on the device
     // every hit whose distance is above the endpoint's current best[] (it can never be part of the answer).
@@ -313,7 +336,7 @@ struct NNContext {
     bool fixed = false;            // NNParams::fixed
     bool dev_excluded(uint32_t q) const { return mask_exc && is_exc(q); }
     bool flags_dirty = false;      // a wide stage left its own query flags on the device
-    bool roles_uniform = false;    // 1-set, no is_converged: every entry is query and target
+    bool roles_uniform = false;    // 1-set, no converged entry: every entry is query and target
     // isocon_nn_graph: constant role flags are not filled by nn_setup but with the start of the first pass (begin_pass), or by
     // flush_flags() in front of anything else that reads them on the device
     bool defer_flags = false, flags_deferred = false;
@@ -417,15 +440,15 @@ int nn_setup(NNContext &C, isocon_store *s, const uint8_t *is_converged, const u
     for (uint32_t i = 1; i < n; ++i)
         if (s->lens[i] < s->lens[i - 1]) { g_last_error = "nearest-neighbour entry points need a length-sorted store"; return ISOCON_E_ARG; }
     C.two_set = is_target != nullptr;
-    C.roles_uniform = !C.two_set && !is_converged;
     C.min_d = C.two_set ? 0 : 1;
     C.qflag.assign(n, 0);
     C.tflag.assign(n, 0);
-    uint64_t n_targets = 0;
+    uint64_t n_targets = 0, n_converged = 0;
     for (uint32_t i = 0; i < n; ++i) {
         if (C.two_set) { C.tflag[i] = is_target[i] ? 1 : 0; C.qflag[i] = is_target[i] ? 0 : 1; n_targets += C.tflag[i]; }
-        else { C.tflag[i] = 1; C.qflag[i] = (is_converged && is_converged[i]) ? 0 : 1; }
+        else { C.tflag[i] = 1; C.qflag[i] = (is_converged && is_converged[i]) ? 0 : 1; n_converged += C.qflag[i] == 0; }
     }
+    C.roles_uniform = !C.two_set && n_converged == 0;          // (the wrappers always pass is_converged: mostly all zero)
     if (C.two_set) {
         // NNG:416 stops after `depth` candidate alignments (an order-dependent rule): the passes of this context are exact only when it
         // cannot bind.  depth_walk: the caller (isocon_nn_graph) sends such a call through nn2_depth_graph, which carries the rule out.
@@ -448,7 +471,7 @@ int nn_setup(NNContext &C, isocon_store *s, const uint8_t *is_converged, const u
     int rc;
     if ((rc = C.d_best.alloc((size_t)std::max<uint32_t>(n, 1) * 4)) || (rc = C.d_qf.alloc(std::max<uint32_t>(n, 1))) ||
         (rc = C.d_tf.alloc(std::max<uint32_t>(n, 1))) || (rc = C.d_hits.alloc(C.hits_cap * 12)) || (rc = C.d_hit_count.alloc(8)) ||
-        (rc = C.d_stats.alloc(2 * (NN_COUNTER_SLOTS * 4 + 1) * 8)))
+        (rc = C.d_stats.alloc(NNContext::N_COUNTERS * 8)))
         return rc;
     clk.lap("setup: pool");
     if ((rc = C.upload_flags(true))) return rc;

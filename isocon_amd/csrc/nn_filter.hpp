@@ -156,11 +156,11 @@ __global__ __launch_bounds__(256, ISOCON_NNF_WAVES) void k_nn_block_filter(const
                                                           int32_t kcap, uint32_t *__restrict__ list, const NNChunk *__restrict__ chunks_in, unsigned long long cap_in,
                                                           NNChunk *__restrict__ chunks_out, unsigned long long cap_out, uint32_t *__restrict__ pa, uint32_t *__restrict__ pb,
                                                           unsigned long long small_cap, NNPlanTotals *__restrict__ totals, uint32_t list_min, NNFTask *__restrict__ tasks,
-                                                          unsigned long long tasks_cap)
+                                                          unsigned long long tasks_cap, NNSeedKnown K)
 {
     __shared__ uint32_t bitmap[2048];
     __shared__ uint32_t pass[NN_STAGE];
-    __shared__ uint32_t s_npass;
+    __shared__ uint32_t s_npass, s_nknown, s_cursor;
     __shared__ unsigned long long s_chunk, s_base;
     const int lane = threadIdx.x & 63;
     if (totals->overflow) return;          // (the list builder gave up: its chunk tables have holes)
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(256, ISOCON_NNF_WAVES) void k_nn_block_filter(const
     const unsigned long long nB = totals->n_chunks_narrow < cap_in ? totals->n_chunks_narrow : cap_in;
     for (;;) {
         __syncthreads();          // (the previous chunk's LDS is no longer read)
-        if (threadIdx.x == 0) { s_chunk = atomicAdd(&totals->f_next, 1ull); s_npass = 0; }
+        if (threadIdx.x == 0) { s_chunk = atomicAdd(&totals->f_next, 1ull); s_npass = 0; s_nknown = 0; s_cursor = 0; }
         for (uint32_t i = threadIdx.x; i < 2048; i += 256) bitmap[i] = 0xffffffffu;
         __syncthreads();
         const unsigned long long c = nnf_uniform64(s_chunk);          // (scalar: the chunk record, its owner and the loop bounds stay out of the vector registers)
@@ -204,6 +204,20 @@ __global__ __launch_bounds__(256, ISOCON_NNF_WAVES) void k_nn_block_filter(const
         // what is left stays a chunk for the table kernels when it is enough for a table AND the test rejected less than half of the chunk (a set on
         // which the grams decide little); otherwise the second pass looks at it, or -- a handful -- it joins the flat pairs as it is
         const bool to_table = np >= list_min && (tasks == nullptr || 2u * np >= ch.count);
+        // flat pairs: the ones the seed pass has settled are marked (NNSeedKnown; no list word is 0xffffffff: indices are below 2^30) and stay behind
+        const bool flat_known = K.known != nullptr && !to_table && !(tasks != nullptr && np >= NNF_PASS2_MIN) && np != 0;          // (uniform)
+        if (flat_known) {
+            for (uint32_t i0 = (threadIdx.x >> 6) * 64u; i0 < np; i0 += 256u) {
+                const uint32_t i = i0 + (uint32_t)lane;
+                const bool settled = i < np && nn_seed_known(K.known, x, pass[i] & 0x3fffffffu);
+                const uint32_t ns = (uint32_t)__popcll(__ballot(settled));
+                if (lane == 0 && ns) atomicAdd(&s_nknown, ns);
+                if (settled && K.drop) pass[i] = 0xffffffffu;
+            }
+            __syncthreads();
+        }
+        const uint32_t n_known = flat_known ? (uint32_t)__builtin_amdgcn_readfirstlane((int)s_nknown) : 0u;
+        const uint32_t n_flat = K.drop ? np - n_known : np;          // (flat pairs that leave)
         if (threadIdx.x == 0) {
             unsigned long long base = 0;
             if (to_table) {
@@ -217,10 +231,11 @@ __global__ __launch_bounds__(256, ISOCON_NNF_WAVES) void k_nn_block_filter(const
                 const uint32_t nt = (np + 63u) / 64u;
                 base = atomicAdd(&totals->f_tasks, (unsigned long long)nt);
                 if (base + nt > tasks_cap) { atomicOr(&totals->overflow, 1ull); base = ~0ull; }
-            } else if (np) {
-                base = atomicAdd(&totals->n_small, (unsigned long long)np);
-                if (base + np > small_cap) { atomicOr(&totals->overflow, 1ull); base = ~0ull; }
+            } else if (n_flat) {
+                base = atomicAdd(&totals->n_small, (unsigned long long)n_flat);
+                if (base + n_flat > small_cap) { atomicOr(&totals->overflow, 1ull); base = ~0ull; }
             }
+            if (n_known) atomicAdd(&totals->n_seed_known, (unsigned long long)n_known);
             s_base = base;
         }
         if ((threadIdx.x & 63) == 0 && rejected) atomicAdd(&totals->f_rejected, (unsigned long long)rejected);
@@ -235,7 +250,19 @@ __global__ __launch_bounds__(256, ISOCON_NNF_WAVES) void k_nn_block_filter(const
                     tasks[base + j] = t;
                 }
             }
-            else { for (uint32_t i = threadIdx.x; i < np; i += 256) { pa[base + i] = x; pb[base + i] = pass[i] & 0x3fffffffu; } }
+            else if (n_flat == np) { for (uint32_t i = threadIdx.x; i < np; i += 256) { pa[base + i] = x; pb[base + i] = pass[i] & 0x3fffffffu; } }
+            else {
+                // the unmarked pairs, dense (in any order: a wave takes its 64 places from a cursor)
+                for (uint32_t i0 = (threadIdx.x >> 6) * 64u; i0 < np; i0 += 256u) {
+                    const uint32_t i = i0 + (uint32_t)lane;
+                    const uint32_t word = i < np ? pass[i] : 0xffffffffu;
+                    const uint64_t sm = __ballot(word != 0xffffffffu);
+                    uint32_t first = 0;
+                    if (lane == 0 && sm) first = atomicAdd(&s_cursor, (uint32_t)__popcll(sm));
+                    first = (uint32_t)__builtin_amdgcn_readfirstlane((int)first);
+                    if (word != 0xffffffffu) { const unsigned long long at = base + first + (uint32_t)__popcll(sm & (((uint64_t)1 << lane) - 1)); pa[at] = x; pb[at] = word & 0x3fffffffu; }
+                }
+            }
         }
     }
 }
@@ -247,7 +274,8 @@ __global__ __launch_bounds__(256, ISOCON_NNF_WAVES) void k_nn_block_filter(const
 // pairs of the one-pair-per-lane kernel.  Waves of a workgroup never wait for each other (no barrier: a wave only reads the LDS it wrote).
 __global__ __launch_bounds__(256, 3) void k_nn_block_filter2(const uint32_t *__restrict__ text, uint32_t stride, const int32_t *__restrict__ lens, const uint32_t *__restrict__ meta,
                                                              int32_t kcap, const uint32_t *__restrict__ list, const NNFTask *__restrict__ tasks, unsigned long long tasks_cap,
-                                                             uint32_t *__restrict__ pa, uint32_t *__restrict__ pb, unsigned long long small_cap, NNPlanTotals *__restrict__ totals)
+                                                             uint32_t *__restrict__ pa, uint32_t *__restrict__ pb, unsigned long long small_cap, NNPlanTotals *__restrict__ totals,
+                                                             NNSeedKnown K)
 {
     __shared__ uint32_t bitmaps[4][2048];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -279,18 +307,24 @@ __global__ __launch_bounds__(256, 3) void k_nn_block_filter2(const uint32_t *__r
         }
         const uint32_t cnt = nnf_count<2>(bitmap, text + (size_t)y * stride, active ? nnf_dwords<2>(lens[y]) : 0, k, active);
         const bool keep = active && (int32_t)cnt <= k;
-        const uint64_t km = __ballot(keep);
-        const uint32_t nk = (uint32_t)__popcll(km);
+        const uint32_t nk = (uint32_t)__popcll(__ballot(keep));
+        // of the pairs it keeps, the ones the seed pass has settled do not leave (NNSeedKnown)
+        const bool settled = keep && K.known != nullptr && nn_seed_known(K.known, x, y);
+        const uint32_t n_known = (uint32_t)__popcll(__ballot(settled));
+        const bool leaves = keep && !(settled && K.drop);
+        const uint64_t km = __ballot(leaves);
+        const uint32_t nl = (uint32_t)__popcll(km);
         unsigned long long base = 0;
         if (lane == 0) {
-            if (nk) {
-                base = atomicAdd(&totals->n_small, (unsigned long long)nk);
-                if (base + nk > small_cap) { atomicOr(&totals->overflow, 1ull); base = ~0ull; }
+            if (nl) {
+                base = atomicAdd(&totals->n_small, (unsigned long long)nl);
+                if (base + nl > small_cap) { atomicOr(&totals->overflow, 1ull); base = ~0ull; }
             }
             if (count > nk) atomicAdd(&totals->f_rejected2, (unsigned long long)(count - nk));
+            if (n_known) atomicAdd(&totals->n_seed_known, (unsigned long long)n_known);
         }
         base = nnf_uniform64(base);
-        if (keep && base != ~0ull) {
+        if (leaves && base != ~0ull) {
             const unsigned long long at = base + (unsigned long long)__popcll(km & lt_mask);
             pa[at] = x; pb[at] = y;
         }
@@ -303,33 +337,69 @@ __global__ __launch_bounds__(256, 3) void k_nn_block_filter2(const uint32_t *__r
 // The one place that launches the two kernels -- NNContext::plan_lists and the test entry isocon_block_filter_chunks both come here.
 inline hipError_t nnf_launch_filter(const uint32_t *text, uint32_t stride, const int32_t *lens, const uint32_t *meta, int32_t kcap, uint32_t *list, const NNChunk *chunks_in,
                                     unsigned long long cap_in, NNChunk *chunks_out, unsigned long long cap_out, uint32_t *pa, uint32_t *pb, unsigned long long small_cap,
-                                    NNPlanTotals *totals, uint32_t list_min, NNFTask *tasks, unsigned long long tasks_cap)
+                                    NNPlanTotals *totals, uint32_t list_min, NNFTask *tasks, unsigned long long tasks_cap, NNSeedKnown K)
 {
     hipLaunchKernelGGL(k_nn_block_filter, dim3(NNF_GRID), dim3(256), 0, 0, text, stride, lens, meta, kcap, list, chunks_in, cap_in, chunks_out, cap_out, pa, pb, small_cap, totals, list_min,
-                       tasks, tasks_cap);
+                       tasks, tasks_cap, K);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || tasks == nullptr) return e;
-    hipLaunchKernelGGL(k_nn_block_filter2, dim3(NNF_GRID2), dim3(256), 0, 0, text, stride, lens, meta, kcap, list, tasks, tasks_cap, pa, pb, small_cap, totals);
+    hipLaunchKernelGGL(k_nn_block_filter2, dim3(NNF_GRID2), dim3(256), 0, 0, text, stride, lens, meta, kcap, list, tasks, tasks_cap, pa, pb, small_cap, totals, K);
     return hipGetLastError();
 }
 
 // Few chunks left (the filter rejected nearly everything): a table launch of a few dozen workgroups is one lone wave per SIMD for the length of
 // a whole chunk (1.4 ms for 57 000 pairs at C3), the pair-per-lane kernel takes the same pairs in 0.15 ms.  One workgroup per chunk appends
-// its pairs to the flat arrays (the host adds f_listed to its count of them).
+// its pairs to the flat arrays (the host adds f_listed to its count of them) -- but for the pairs the seed pass has settled (NNSeedKnown): the
+// host has read the totals by now, so their number goes to *known_count (a counter that comes back with the pass' record) and the
+// pair-per-lane launch reads the number of flat pairs on the device (totals->n_small).
 __global__ __launch_bounds__(256) void k_nn_chunks_to_pairs(const NNChunk *__restrict__ chunks, const uint32_t *__restrict__ list, uint32_t *__restrict__ pa, uint32_t *__restrict__ pb,
-                                                             unsigned long long small_cap, NNPlanTotals *__restrict__ totals)
+                                                             unsigned long long small_cap, NNPlanTotals *__restrict__ totals, NNSeedKnown K, unsigned long long *__restrict__ known_count)
 {
     __shared__ unsigned long long s_base;
+    __shared__ uint32_t s_nknown, s_cursor;
     const NNChunk ch = chunks[blockIdx.x];
+    const int lane = threadIdx.x & 63;
+    if (threadIdx.x == 0) { s_nknown = 0; s_cursor = 0; }
+    __syncthreads();
+    // round t of a thread = pair 256 t + threadIdx.x of the chunk, bit t of its mask = settled (a chunk holds at most NN_STAGE pairs)
+    static_assert(NN_STAGE <= 32 * 256, "one mask bit per round of a chunk");
+    uint32_t settled_rounds = 0;
+    if (K.known != nullptr) {
+        for (uint32_t i0 = (threadIdx.x >> 6) * 64u, t = 0; i0 < ch.count; i0 += 256u, ++t) {
+            const uint32_t i = i0 + (uint32_t)lane;
+            const bool settled = i < ch.count && nn_seed_known(K.known, ch.slot, list[ch.begin + i] & 0x3fffffffu);
+            const uint32_t ns = (uint32_t)__popcll(__ballot(settled));
+            if (lane == 0 && ns) atomicAdd(&s_nknown, ns);
+            if (settled) settled_rounds |= 1u << t;
+        }
+        __syncthreads();
+    }
+    const uint32_t n_known = s_nknown, n_out = K.drop ? ch.count - n_known : ch.count;
     if (threadIdx.x == 0) {
-        unsigned long long base = atomicAdd(&totals->n_small, (unsigned long long)ch.count);
-        if (base + ch.count > small_cap) { atomicOr(&totals->overflow, 1ull); base = ~0ull; }
+        unsigned long long base = 0;
+        if (n_out) {
+            base = atomicAdd(&totals->n_small, (unsigned long long)n_out);
+            if (base + n_out > small_cap) { atomicOr(&totals->overflow, 1ull); base = ~0ull; }
+        }
+        if (n_known) atomicAdd(known_count, (unsigned long long)n_known);
         s_base = base;
     }
     __syncthreads();
     const unsigned long long base = s_base;
-    if (base == ~0ull) return;
-    for (uint32_t i = threadIdx.x; i < ch.count; i += 256) { pa[base + i] = ch.slot; pb[base + i] = list[ch.begin + i] & 0x3fffffffu; }
+    if (base == ~0ull || n_out == 0) return;
+    if (n_out == ch.count) { for (uint32_t i = threadIdx.x; i < ch.count; i += 256) { pa[base + i] = ch.slot; pb[base + i] = list[ch.begin + i] & 0x3fffffffu; } }
+    else {
+        // the pairs that stay, dense (in any order: a wave takes its places from a cursor)
+        for (uint32_t i0 = (threadIdx.x >> 6) * 64u, t = 0; i0 < ch.count; i0 += 256u, ++t) {
+            const uint32_t i = i0 + (uint32_t)lane;
+            const bool stays = i < ch.count && ((settled_rounds >> t) & 1u) == 0;
+            const uint64_t sm = __ballot(stays);
+            uint32_t first = 0;
+            if (lane == 0 && sm) first = atomicAdd(&s_cursor, (uint32_t)__popcll(sm));
+            first = (uint32_t)__builtin_amdgcn_readfirstlane((int)first);
+            if (stays) { const unsigned long long at = base + first + (uint32_t)__popcll(sm & (((uint64_t)1 << lane) - 1)); pa[at] = ch.slot; pb[at] = list[ch.begin + i] & 0x3fffffffu; }
+        }
+    }
 }
 
 // The count for explicit (owner, partner) pairs, one workgroup per pair (tests: isocon_block_bound_pairs) -- the same two device functions.

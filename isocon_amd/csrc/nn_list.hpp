@@ -44,7 +44,28 @@ struct NNPlanTotals {
     // the block filter behind the list builder (nn_filter.hpp): its work queue, the chunks it leaves per class, the pairs it rejected
     unsigned long long f_next, pad8[15], f_chunks, pad9[15], f_chunks_narrow, pad10[15], f_rejected, f_narrow_listed, f_listed, f_rejected2, pad11[12];          // f_listed: pairs in the chunks it leaves (both classes); f_rejected2: by its second pass
     unsigned long long f_tasks, pad12[15], f_task_next, pad13[15];          // tasks of the second pass (nn_filter.hpp) and its queue
+    unsigned long long n_seed_known, pad14[15];          // flat pairs that the seed pass of the call had aligned already (NNSeedKnown)
 };
+
+// The seed pairs of the call as a table (written by k_qgram_seed_pairs, qgram_mm.hpp): known[x][0 .. NN_KNOWN_SLOTS) = the other ends of the
+// pairs thread x proposed, 0xffffffff = none.  A pair (a, b) is SETTLED iff b is in known[a] or a is in known[b] (the column candidate a
+// thread drops because the row proposes the same pair is in the row's entry).  The seed pass aligned a settled pair under a threshold
+// that was at least the one the main pass would use (best[] only decreases, same roles, same min_d) and is through before the lists are
+// built: a hit is in the hit list already, a miss stays a miss.  So the kernels that make FLAT pairs -- after every decision of the
+// filters, which see and count a settled pair as ever -- leave it out of the pair arrays (drop != 0) or only count it (drop == 0:
+// nn_seed_skip=0 / =count).  known == nullptr: no table (2-set, is_converged, fixed thresholds, images, seeds of another call).
+static constexpr uint32_t NN_KNOWN_SLOTS = 8;
+struct NNSeedKnown { const uint32_t *known; uint32_t drop; };
+typedef uint32_t NNKnownRow __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ bool nn_seed_known(const uint32_t *__restrict__ known, uint32_t a, uint32_t b)
+{
+    const NNKnownRow *ra = reinterpret_cast<const NNKnownRow *>(known + (size_t)a * NN_KNOWN_SLOTS), *rb = reinterpret_cast<const NNKnownRow *>(known + (size_t)b * NN_KNOWN_SLOTS);
+    const NNKnownRow a0 = ra[0], a1 = ra[1], b0 = rb[0], b1 = rb[1];
+    bool hit = false;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) hit = hit || a0[i] == b || a1[i] == b || b0[i] == a || b1[i] == a;
+    return hit;
+}
 
 // Threshold classes of the listed launch.  A pair whose threshold max(k of its two directions) is <= NN_NARROW_K is exact on 32
 // diagonals (a path of cost <= k stays inside k + 1 of them), and on 32-bit vectors the table kernel's column is 12 instead of 21
@@ -91,14 +112,14 @@ __global__ __launch_bounds__(256) void k_nn_entry_meta(DevStore S, NNParams P, c
 // same best[], bound), and the same ownership rule -- the end with the larger hub score, ties to the lower index -- so every
 // surviving pair is kept by exactly one of its two ends.  Kept pairs are staged in LDS; NN_LIST_CHUNK staged pairs become a chunk
 // of `list` (one k_nn_scan_refill workgroup with x's table), what is left at the end becomes a last chunk if it has NN_LIST_MIN
-// pairs, else flat pairs for the one-pair-per-lane kernel.
+// pairs, else flat pairs for the one-pair-per-lane kernel -- those of them that the seed pass has not settled (K).
 __global__ __launch_bounds__(64 * NN_SURV_WAVES) void k_nn_survivors(DevStore S, NNParams P, NNBoundRows B, const uint32_t *__restrict__ meta, QMap Q, uint32_t nq,
                                                        uint32_t *__restrict__ list, unsigned long long list_cap, NNChunk *__restrict__ chunks, unsigned long long chunks_cap,
                                                        uint32_t *__restrict__ pa, uint32_t *__restrict__ pb, unsigned long long small_cap, NNPlanTotals *__restrict__ totals, uint32_t list_min,
-                                                       int32_t class_mode)
+                                                       int32_t class_mode, NNSeedKnown K)
 {
     __shared__ uint32_t stage[NN_SURV_WAVES][NN_STAGE];
-    __shared__ uint32_t s_small[NN_SURV_WAVES], s_filtered[NN_SURV_WAVES], s_kept[NN_SURV_WAVES];
+    __shared__ uint32_t s_small[NN_SURV_WAVES], s_filtered[NN_SURV_WAVES], s_kept[NN_SURV_WAVES], s_known[NN_SURV_WAVES];
     __shared__ unsigned long long s_base;
     const int wave = threadIdx.x >> 6;
     const uint32_t x = blockIdx.x * (uint32_t)NN_SURV_WAVES + (uint32_t)wave;
@@ -274,11 +295,25 @@ __global__ __launch_bounds__(64 * NN_SURV_WAVES) void k_nn_survivors(DevStore S,
     // what is left goes to the pair arrays: one allocation per workgroup
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { filtered += __shfl_xor(filtered, o, 64); kept += __shfl_xor(kept, o, 64); }          // (counted per lane in the scan)
-    if (lane == 0) { s_small[wave] = rest; s_filtered[wave] = filtered; s_kept[wave] = kept; }
+    // ... but for the pairs the seed pass has settled (NNSeedKnown): round t of a lane = item 64 t + lane, bit t of its mask = settled
+    static_assert(NN_STAGE <= 64 * 64, "one mask bit per round of the staged pairs");
+    const auto item = [&](uint32_t i) { return (i < fill ? st[i] : st[NN_STAGE - 1 - (i - fill)]) & 0x3fffffffu; };
+    uint64_t settled_rounds = 0;
+    uint32_t n_known = 0;          // (wave-uniform)
+    if (K.known != nullptr) {
+        for (uint32_t i0 = 0, t = 0; i0 < rest; i0 += 64, ++t) {
+            const uint32_t i = i0 + (uint32_t)lane;
+            const bool settled = i < rest && nn_seed_known(K.known, x, item(i));
+            n_known += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(settled));
+            if (settled) settled_rounds |= (uint64_t)1 << t;
+        }
+    }
+    const uint32_t n_out = K.drop ? rest - n_known : rest;
+    if (lane == 0) { s_small[wave] = n_out; s_filtered[wave] = filtered; s_kept[wave] = kept; s_known[wave] = n_known; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        uint32_t tot = 0, fsum = 0, ksum = 0;
-        for (int w = 0; w < NN_SURV_WAVES; ++w) { tot += s_small[w]; fsum += s_filtered[w]; ksum += s_kept[w]; }
+        uint32_t tot = 0, fsum = 0, ksum = 0, nsum = 0;
+        for (int w = 0; w < NN_SURV_WAVES; ++w) { tot += s_small[w]; fsum += s_filtered[w]; ksum += s_kept[w]; nsum += s_known[w]; }
         unsigned long long base = 0;
         if (tot) {
             base = atomicAdd(&totals->n_small, (unsigned long long)tot);
@@ -287,12 +322,24 @@ __global__ __launch_bounds__(64 * NN_SURV_WAVES) void k_nn_survivors(DevStore S,
         s_base = base;
         if (fsum) atomicAdd(&totals->n_filtered, (unsigned long long)fsum);
         if (ksum) atomicAdd(&totals->n_pairs, (unsigned long long)ksum);
+        if (nsum) atomicAdd(&totals->n_seed_known, (unsigned long long)nsum);
     }
     __syncthreads();
-    if (rest && s_base != ~0ull) {
+    if (n_out && s_base != ~0ull) {
         unsigned long long base = s_base;
         for (int w = 0; w < wave; ++w) base += s_small[w];
-        for (uint32_t i = (uint32_t)lane; i < rest; i += 64) { pa[base + i] = x; pb[base + i] = (i < fill ? st[i] : st[NN_STAGE - 1 - (i - fill)]) & 0x3fffffffu; }
+        if (n_out == rest) { for (uint32_t i = (uint32_t)lane; i < rest; i += 64) { pa[base + i] = x; pb[base + i] = item(i); } }
+        else {
+            // the pairs that stay, dense: a round's survivors behind those of the rounds before
+            const uint64_t below = ((uint64_t)1 << lane) - 1;
+            for (uint32_t i0 = 0, t = 0; i0 < rest; i0 += 64, ++t) {
+                const uint32_t i = i0 + (uint32_t)lane;
+                const bool stays = i < rest && ((settled_rounds >> t) & 1u) == 0;
+                const uint64_t sm = __builtin_amdgcn_ballot_w64(stays);
+                if (stays) { const unsigned long long at = base + (unsigned long long)__popcll(sm & below); pa[at] = x; pb[at] = item(i); }
+                base += (unsigned long long)__popcll(sm);
+            }
+        }
     }
 }
 

@@ -43,20 +43,21 @@ int NNContext::plan_lists(const QMap &Q, uint32_t nq, const NNParams &PR, ListPl
     B.sloT = static_cast<const uint32_t *>(st->pool.slots[SLOT_NN_LBT_SLO].p);
     B.lenT = static_cast<const uint32_t *>(st->pool.slots[SLOT_NN_LBT_LEN].p);
     B.score = static_cast<const uint32_t *>(st->pool.slots[SLOT_NN_SCORE].p);
+    const NNSeedKnown K = seed_known();          // the pairs the seed pass of this pass has settled do not become flat pairs again
     tm.start();
     int32_t class_mode = 0;          // variant nn_narrow=0: every pair on 64 rows; =1: pairs above 31 leave the lists for the pair-per-lane kernel (nn_list.hpp)
     if (const char *e = variant_value("nn_narrow")) class_mode = atoi(e) > 0 ? 1 : -1;
     hipLaunchKernelGGL(k_nn_entry_meta, dim3((n + NN_META_PAD + 255) / 256), dim3(256), 0, 0, st->dev, PR, B.score, d_lmeta.as<uint32_t>(), d_ltot.as<NNPlanTotals>());
     ISO_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(k_nn_survivors, dim3((n + NN_SURV_WAVES - 1) / NN_SURV_WAVES), dim3(64 * NN_SURV_WAVES), 0, 0, st->dev, PR, B, d_lmeta.as<uint32_t>(), Q, nq, d_list.as<uint32_t>(), pairs_cap,
-                       filter ? built : L.a, cap_in, d_lpa.as<uint32_t>(), d_lpb.as<uint32_t>(), pairs_cap, d_ltot.as<NNPlanTotals>(), build_min, class_mode);
+                       filter ? built : L.a, cap_in, d_lpa.as<uint32_t>(), d_lpb.as<uint32_t>(), pairs_cap, d_ltot.as<NNPlanTotals>(), build_min, class_mode, K);
     ISO_HIP_CHECK(hipGetLastError());
     if (filter) {
         // one launch over a work queue of the builder's chunks (their number is only known on the device)
         tm.mark();
         ISO_HIP_CHECK(nnf_launch_filter(d_text2.as<uint32_t>(), text2_stride, st->dev.lens, d_lmeta.as<uint32_t>(), PR.kcap, d_list.as<uint32_t>(), built, cap_in, L.a, cap_out,
                                         d_lpa.as<uint32_t>(), d_lpb.as<uint32_t>(), pairs_cap, d_ltot.as<NNPlanTotals>(), list_min,
-                                        second ? d_ltasks.as<NNFTask>() : (NNFTask *)nullptr, tasks_cap));
+                                        second ? d_ltasks.as<NNFTask>() : (NNFTask *)nullptr, tasks_cap, K));
     }
     tm.stop_later(&stats.list_kernel_ms, &stats.filter_kernel_ms);          // (the filter's part of list_kernel_ms; the context's own marked time is narrow_kernel_ms)
     // (the interval closes in front of the copy of the totals, not behind it as it used to: list_kernel_ms is the kernels' time alone)
@@ -70,6 +71,8 @@ int NNContext::plan_lists(const QMap &Q, uint32_t nq, const NNParams &PR, ListPl
     L.n_chunks = filter ? tot.f_chunks : tot.n_chunks;
     L.n_chunks_narrow = filter ? tot.f_chunks_narrow : tot.n_chunks_narrow;
     L.n_small = tot.n_small;
+    L.seed_known = tot.n_seed_known;
+    L.K = K;
     stats.pairs_wide_to_lanes += tot.n_wide_pairs;
     unsigned long long table_chunks = NNF_TABLE_CHUNKS;
     if (const char *e = variant_value("nn_table_chunks")) table_chunks = strtoull(e, nullptr, 10);          // A/B runs, tests (0: tables whatever is left)

@@ -88,6 +88,7 @@ int phase_a_seeds(NNContext &C, const QMap &Q, PhaseAPass &P, HostClock &clk)
 int regroup_by_seed_hits(NNContext &C, const std::vector<int32_t> &best_at_entry, Regrouped &G, HostClock &clk)
 {
     const uint32_t n = C.n;
+    C.known_ready = false;          // (the seed pairs' table speaks of the caller's positions and of a hit list that is collected here)
     uint64_t needed0 = 0;
     std::vector<int32_t> seed_hits;
     int rc = C.collect(seed_hits, &needed0);
@@ -184,21 +185,32 @@ int run_listed_pass(NNContext &C, const QMap &Q, const NNParams &PR, const NNCon
         PL.stats = C.d_stats.as<unsigned long long>() + (NN_COUNTER_SLOTS * 4 + 1);
         if ((rc = launch_refill(C, nn_refill_shape(C.st->maxlen, lw ? atoi(lw) : 8, true), true, (unsigned)LP.n_chunks_narrow, PL, Q, 0))) return rc;
     }
+    // The flat pairs: what the list builder and the filter left (LP.n_small, the pairs the seed pass has settled taken out already) and the
+    // pairs of the converted chunks -- of those the host knows only the upper bound conv_pairs: k_nn_chunks_to_pairs takes the settled
+    // ones out too, and the lane launch reads the number that is left on the device (no further wait of the host).
     const unsigned long long n_small = LP.n_small + LP.conv_pairs;
+    const unsigned long long dropped = LP.K.drop ? LP.seed_known : 0;          // reached this stage and were not aligned a second time
     if (n_small) {
         C.tm.stop_later(&C.stats.scan_kernel_ms);
         C.tm.start();
         const unsigned long long pairs_cap = C.st->pool.slots[SLOT_NN_LPA].cap / 4;
-        if (LP.conv_a) hipLaunchKernelGGL(k_nn_chunks_to_pairs, dim3((unsigned)LP.conv_a), dim3(256), 0, 0, LP.a, C.d_list.as<uint32_t>(), C.d_lpa.as<uint32_t>(), C.d_lpb.as<uint32_t>(), pairs_cap, C.d_ltot.as<NNPlanTotals>());
-        if (LP.conv_b) hipLaunchKernelGGL(k_nn_chunks_to_pairs, dim3((unsigned)LP.conv_b), dim3(256), 0, 0, LP.b, C.d_list.as<uint32_t>(), C.d_lpa.as<uint32_t>(), C.d_lpb.as<uint32_t>(), pairs_cap, C.d_ltot.as<NNPlanTotals>());
+        unsigned long long *known_count = C.d_stats.as<unsigned long long>() + NNContext::KNOWN_COUNTER;
+        const unsigned long long *live = nullptr;
+        if (LP.conv_a) hipLaunchKernelGGL(k_nn_chunks_to_pairs, dim3((unsigned)LP.conv_a), dim3(256), 0, 0, LP.a, C.d_list.as<uint32_t>(), C.d_lpa.as<uint32_t>(), C.d_lpb.as<uint32_t>(), pairs_cap, C.d_ltot.as<NNPlanTotals>(), LP.K, known_count);
+        if (LP.conv_b) hipLaunchKernelGGL(k_nn_chunks_to_pairs, dim3((unsigned)LP.conv_b), dim3(256), 0, 0, LP.b, C.d_list.as<uint32_t>(), C.d_lpa.as<uint32_t>(), C.d_lpb.as<uint32_t>(), pairs_cap, C.d_ltot.as<NNPlanTotals>(), LP.K, known_count);
+        if ((LP.conv_a || LP.conv_b) && LP.K.drop) live = &C.d_ltot.as<NNPlanTotals>()->n_small;
         hipLaunchKernelGGL(k_ed_lanes<true>, dim3((unsigned)((n_small + 255) / 256)), dim3(256), 0, 0, C.st->dev, C.params(63), C.d_lpa.as<uint32_t>(), C.d_lpb.as<uint32_t>(),
-                           (const int32_t *)nullptr, (uint64_t)n_small, (int32_t *)nullptr);
+                           (const int32_t *)nullptr, (uint64_t)n_small, (int32_t *)nullptr, live);
         ISO_HIP_CHECK(hipGetLastError());
         C.tm.stop_later(&C.stats.lanes_kernel_ms);
-        C.stats.pairs_evaluated += n_small;
-        C.stats.pairs_lanes += n_small;
         C.tm.start();
     }
+    // pairs_evaluated / pairs_lanes: the pairs that reached the alignment stage, settled ones included; pairs_lanes_aligned: what the launch
+    // ran (the settled pairs of the converted chunks leave it when their counter arrives, NNContext::add_counters)
+    C.stats.pairs_evaluated += n_small + dropped;
+    C.stats.pairs_lanes += n_small + dropped;
+    C.stats.pairs_seed_known += LP.seed_known;
+    C.stats.pairs_lanes_aligned += n_small;
     return ISOCON_OK;
 }
 

@@ -601,15 +601,17 @@ __global__ __launch_bounds__(512, 2) void k_qgram_mm(const uint8_t *__restrict__
 #endif
 }
 
-// The fills in front of k_qgram_mm in one launch (hub scores, row / column minima, the seed arrays and their counter: six fills cost the
-// host 50 us of enqueueing on the path that bounds the start of k_qgram_mm): range r = `words` dwords of `value`; unused ranges have 0 words.
+// The fills in front of k_qgram_mm in one launch (hub scores, row / column minima, the seed arrays, their counter and the table of the
+// seed pairs: six fills cost the host 50 us of enqueueing on the path that bounds the start of k_qgram_mm): range r = `words` dwords of
+// `value`; unused ranges have 0 words.
 struct QMFillRange { uint32_t *p; unsigned long long words; uint32_t value; };
-struct QMFills { QMFillRange r[6]; };
+static constexpr int QM_FILL_RANGES = 7;
+struct QMFills { QMFillRange r[QM_FILL_RANGES]; };
 __global__ __launch_bounds__(256) void k_qm_fills(QMFills F)
 {
     const unsigned long long first = (unsigned long long)blockIdx.x * 256u + threadIdx.x, step = (unsigned long long)gridDim.x * 256u;
 #pragma unroll
-    for (int k = 0; k < 6; ++k)
+    for (int k = 0; k < QM_FILL_RANGES; ++k)
         for (unsigned long long i = first; i < F.r[k].words; i += step) F.r[k].p[i] = F.r[k].value;
 }
 
@@ -649,9 +651,12 @@ __global__ __launch_bounds__(256) void k_lbt_offsets(uint32_t n, const uint32_t 
 // col_classes (1, 2 or QM_SEEDS): the column minima of the QM_SEEDS tile classes are merged into this many candidates.  One GPU keeps
 // all of them; N ranks each see only their own rows of a column, so together they would propose N QM_SEEDS candidates per column --
 // N times the seed work of one GPU, constant per rank: with QM_SEEDS / N classes (at least one) the total stays near one GPU's.
+// known (nullptr: none): the table of the seed pairs the main pass consults (nn_seed_known, nn_list.hpp) -- every pair thread x emits
+// has x as one end, so known[x][i] = the OTHER end of its i-th pair; the slots it does not write keep their fill, 0xffffffff = none.
 __global__ __launch_bounds__(256) void k_qgram_seed_pairs(const unsigned long long *__restrict__ rowmin, const unsigned long long *__restrict__ colmin,
                                                            uint32_t n, QMap Q, uint32_t nq, uint32_t col_classes,
-                                                           uint32_t *__restrict__ pa, uint32_t *__restrict__ pb, unsigned long long *__restrict__ count)
+                                                           uint32_t *__restrict__ pa, uint32_t *__restrict__ pb, unsigned long long *__restrict__ count,
+                                                           uint32_t *__restrict__ known)
 {
     const uint32_t x = blockIdx.x * 256u + threadIdx.x;
     const int lane = threadIdx.x & 63;
@@ -683,6 +688,11 @@ __global__ __launch_bounds__(256) void k_qgram_seed_pairs(const unsigned long lo
                 if (kq == ~0ull || q + 1u + (uint32_t)kq != x) { sa[m] = q; sb[m] = x; ++m; }
             }
         }
+    }
+    if (known != nullptr) {
+#pragma unroll
+        for (uint32_t i = 0; i < 2 * QM_SEEDS; ++i)
+            if (i < m) known[(size_t)x * (2 * QM_SEEDS) + i] = sa[i] == x ? sb[i] : sa[i];
     }
     // wave-aggregated append
     uint32_t inc = m;

@@ -124,8 +124,8 @@ def classify(rows):
 sq, fetch, write = dispatches("sq"), dispatches("fetch"), dispatches("write")
 sys.path.insert(0, ROOT)
 import bench as _bench                      # source_digest(): the kernel sources these counters belong to
-counters = {"round": tag, "source_digest": _bench.source_digest(), "command": "rocprofv3 --pmc <counters> --kernel-trace -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline "
-                                     "(three passes: SQ_*, FETCH_SIZE, WRITE_SIZE)", "workload": "C3 (50k x 2.5kb, seed 30001)"}
+counters = {"round": tag, "source_digest": _bench.source_digest(), "command": "rocprofv3 --pmc <counters> -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline "
+                                     "(three passes without tracing: SQ_*, FETCH_SIZE, WRITE_SIZE)", "workload": "C3 (50k x 2.5kb, seed 30001)"}
 lines = [counters["command"], "dispatches of one NN-graph step at C3 (50k x 2.5kb) and of bench.py's untimed extras"]
 for kind, rows in (("sq", sq), ("fetch", fetch), ("write", write)):
     for did, name, grid, dur, c in rows:
