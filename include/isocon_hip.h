@@ -403,6 +403,30 @@ int isocon_hw_pairs_wide(isocon_store *s, const uint32_t *q, const uint32_t *t, 
                          int32_t *out, float *kernel_ms);
 
 /*
+ * The candidate-vs-candidate graph with ignored ends from the store alone: the pair list of get_all_NN
+ * (modules/end_invariant_functions.py:622-681), the end rules of edlib_traceback (:593-620) and, with symmetric != 0, the symmetrisation
+ * of get_NN_graph_ignored_ends_edlib (:757-788) on the device -- no pair list goes up, no per-pair rows come down.
+ * The store must be in ascending length order (ISOCON_E_ARG otherwise).  Entry i visits the offsets j = 1, 2, ... (i - j before i + j;
+ * a side ends for good at the first length difference above `window` or at the list's end; the offsets stop at max(1, min(depth, n))).
+ * Every visited pair (query i inside target t) gets the row isocon_hw_pairs returns for it with threshold k, and from it
+ *   adj = ed + max(0, start - T) + max(0, len_t - (end + 1) - T) - min(trailing I run, T) - min(leading I run, T),  T = end_threshold;
+ * i -> t is a directed edge iff ed >= 0 and 0 <= adj <= max_ed.  Row i = out_cols / out_ed [out_row_ptr[i] .. out_row_ptr[i + 1]):
+ *   symmetric == 0: the directed edges of i in visit order with adj (get_all_NN on the whole list);
+ *   symmetric != 0: the directed edges of i in visit order, each with min(adj(i -> t), adj(t -> i)) where t -> i is a directed edge too,
+ *     then every t with a directed edge t -> i and none i -> t, in ascending t with adj(t -> i) (the dict of dicts the reference ends
+ *     with, insertion order included).
+ * Limits: window + 2 k + 1 <= 512 diagonals and at most 0xfffffff0 pairs, else ISOCON_E_UNSUPPORTED (so when the tiles cannot be formed
+ * on the device); a store of more than four symbols ISOCON_E_ALPHABET, with the message of isocon_hw_pairs; negative parameters
+ * ISOCON_E_ARG.  ISOCON_E_CAPACITY + *n_edges_needed when edges_cap is too small (out_row_ptr and the counters are valid then); the
+ * number of ordered window pairs bounds the edges in both forms.
+ * out_counters (5 values, or NULL): pairs, pairs that needed a kernel, hits (ed >= 0), directed edges, appended entries (second part of
+ * the symmetric rows).  *kernel_ms sums the enumeration, alignment and edge kernels.
+ */
+int isocon_hw_window_graph(isocon_store *s, int32_t window, int32_t k, uint64_t depth, int32_t end_threshold, int32_t max_ed,
+                           int32_t symmetric, uint64_t *out_row_ptr /* n + 1 */, uint32_t *out_cols, int32_t *out_ed,
+                           uint64_t edges_cap, uint64_t *n_edges_needed, uint64_t *out_counters, float *kernel_ms);
+
+/*
  * edlib.align(q, t, mode="NW", task="path", k) for a pair list (modules/edlib_alignment_module.py:130-135 edlib_traceback).
  * k NULL or k[p] < 0: unbounded.  out_ed[p] = distance, or -1 above k (then the pair has no ops).  Pair p owns
  * out_ops[out_ops_ptr[p] .. out_ops_ptr[p + 1]), len << 4 | code (0 '=', 1 'X', 2 'I' query only, 3 'D' target only), forward order,

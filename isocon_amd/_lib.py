@@ -17,8 +17,10 @@ _SOURCES = sorted(f for f in os.listdir(SRC_DIR) if f.endswith((".hip", ".hpp", 
 
 ISOCON_OK = 0
 ISOCON_E_ARG = -1
+ISOCON_E_ALPHABET = -2
 ISOCON_E_CAPACITY = -4
 ISOCON_E_NODEVICE = -5
+ISOCON_E_UNSUPPORTED = -6
 NN_INF = 0x3FFFFFFF
 
 u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -105,6 +107,8 @@ SYMBOLS = {
                                           ctypes.POINTER(ctypes.c_int64), f32p]),
     "isocon_hw_pairs": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, i32p, ctypes.c_uint64, i32p, f32p]),
     "isocon_hw_pairs_wide": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, i32p, ctypes.c_uint64, i32p, f32p]),
+    "isocon_hw_window_graph": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                              u64p, u32p, i32p, ctypes.c_uint64, u64p, u64p, f32p]),
     "isocon_ed_path_pairs": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, i32p, ctypes.c_uint64, i32p, u32p, u64p, ctypes.c_uint64, u64p, f32p]),
     "isocon_hw_path_pairs": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, i32p, ctypes.c_uint64, i32p, u32p, u64p, ctypes.c_uint64, u64p, f32p]),
     "isocon_readtab_create": (ctypes.c_int, [u8p, u8p, u64p, ctypes.c_uint32, u32p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p), u32p, f32p]),
@@ -243,13 +247,15 @@ def load():
 
 
 class IsoconError(RuntimeError):
-    pass
+    status = None          # the isocon_status of the call that failed, where check() raised it
 
 
 def check(rc: int, what: str):
     if rc != ISOCON_OK:
         L = load()
-        raise IsoconError("%s failed: %s (%s)" % (what, L.isocon_strerror(rc).decode(), L.isocon_last_error().decode()))
+        err = IsoconError("%s failed: %s (%s)" % (what, L.isocon_strerror(rc).decode(), L.isocon_last_error().decode()))
+        err.status = rc
+        raise err
 
 
 def lib():

@@ -225,17 +225,18 @@ int hw_device_tiles(isocon_store *st, uint64_t n_pairs, const uint32_t *d_q, con
     return ISOCON_OK;
 }
 
-// Tiles built on the device (hw_tiles.hpp): the pair arrays go up once, the (n_pairs, 5) result comes down once.
+// The rows of pair lists that are already in device memory (d_q, d_t, d_k: n_pairs entries each), tiles built on the device
+// (hw_tiles.hpp): *d_rows = the (n_pairs, 5) result in the pool's SLOT_HW_OUT, good until the next call that takes that slot.
 // Returns ISOCON_E_UNSUPPORTED with *retry_host set when only the host's greedy cut can form the tiles.
-int hw_pairs_device_tiles(isocon_store *s, const uint32_t *q, const uint32_t *t, const int32_t *k, uint64_t n_pairs, int32_t *out, float *kernel_ms,
-                          bool *retry_host)
+int hw_pairs_device_core(isocon_store *s, const uint32_t *d_q, const uint32_t *d_t, const int32_t *d_k, uint64_t n_pairs, int32_t **d_rows, float *kernel_ms,
+                         bool *retry_host)
 {
     *retry_host = false;
     const uint32_t n = s->dev.n;
     if ((uint64_t)n * 4 >= 0xfffffff0ull) { *retry_host = true; return ISOCON_E_UNSUPPORTED; }
     HostClock clk;
     ScratchPool *pl = &g_scratch;
-    DevBuf d_q(pl, SLOT_HW_PQ), d_t(pl, SLOT_HW_T), d_k(pl, SLOT_HW_K), d_he(pl, SLOT_HW_Q), d_out(pl, SLOT_HW_OUT), d_trace(pl, SLOT_HW_TRACE);
+    DevBuf d_he(pl, SLOT_HW_Q), d_out(pl, SLOT_HW_OUT), d_trace(pl, SLOT_HW_TRACE);
     DevBuf d_tq(pl, SLOT_HW_TILEQ), d_lp(pl, SLOT_HW_LANES), d_key(pl, SLOT_HW_KEY), d_hist(pl, SLOT_HW_HIST), d_cursor(pl, SLOT_HW_CURSOR),
         d_tbase(pl, SLOT_HW_TBASE), d_cls(pl, SLOT_HW_CLS), d_ctr(pl, SLOT_HW_CTR);
     const uint32_t n_keys = n * 4u;
@@ -243,15 +244,11 @@ int hw_pairs_device_tiles(isocon_store *s, const uint32_t *q, const uint32_t *t,
     if (max_tiles64 > 0x7fffff00ull) { *retry_host = true; return ISOCON_E_UNSUPPORTED; }
     const uint32_t max_tiles = (uint32_t)max_tiles64;
     int rc;
-    if ((rc = d_q.alloc(n_pairs * 4)) || (rc = d_t.alloc(n_pairs * 4)) || (rc = d_k.alloc(n_pairs * 4)) || (rc = d_he.alloc(n_pairs * 8)) ||
+    if ((rc = d_he.alloc(n_pairs * 8)) ||
         (rc = d_out.alloc(n_pairs * 20)) || (rc = d_key.alloc(n_pairs * 4)) || (rc = d_hist.alloc((size_t)n_keys * 4)) || (rc = d_cursor.alloc((size_t)n_keys * 4)) ||
         (rc = d_tbase.alloc(((size_t)n_keys + 1) * 4)) || (rc = d_tq.alloc((size_t)max_tiles * 4)) || (rc = d_lp.alloc((size_t)max_tiles * 256)) ||
         (rc = d_cls.alloc((size_t)max_tiles * 16)) || (rc = d_ctr.alloc(sizeof(HwTileCounters))))
         return rc;
-    ISO_HIP_CHECK(copy_h2d(d_q.p, q, n_pairs * 4));
-    ISO_HIP_CHECK(copy_h2d(d_t.p, t, n_pairs * 4));
-    ISO_HIP_CHECK(copy_h2d(d_k.p, k, n_pairs * 4));
-    clk.lap("hw: pair arrays up");
     EventTimer tm;
     HwTileCounters ctr;
     auto flag_error = [&](uint32_t flags) -> int {
@@ -265,13 +262,13 @@ int hw_pairs_device_tiles(isocon_store *s, const uint32_t *q, const uint32_t *t,
     };
     auto tile_in = [&](int c, const HwTileCounters &cc) {
         HwTileIn in{};
-        in.tile_q = d_tq.as<uint32_t>(); in.lane_pair = d_lp.as<uint32_t>(); in.pt = d_t.as<uint32_t>(); in.pk = d_k.as<int32_t>();
+        in.tile_q = d_tq.as<uint32_t>(); in.lane_pair = d_lp.as<uint32_t>(); in.pt = d_t; in.pk = d_k;
         in.n_tiles = cc.cls[c]; in.tile_list = d_cls.as<uint32_t>() + (size_t)c * max_tiles; in.flags = &d_ctr.as<HwTileCounters>()->flags;
         return in;
     };
     // ---- LOCATE ----
     tm.start();
-    if ((rc = hw_device_tiles<0>(s, n_pairs, d_q.as<uint32_t>(), d_t.as<uint32_t>(), d_k.as<int32_t>(), d_he.as<int32_t>(), d_out.as<int32_t>(), d_key.as<uint32_t>(),
+    if ((rc = hw_device_tiles<0>(s, n_pairs, d_q, d_t, d_k, d_he.as<int32_t>(), d_out.as<int32_t>(), d_key.as<uint32_t>(),
                                  d_hist.as<uint32_t>(), d_cursor.as<uint32_t>(), d_tbase.as<uint32_t>(), n_keys, d_tq.as<uint32_t>(), d_lp.as<uint32_t>(), max_tiles,
                                  d_cls.as<uint32_t>(), d_ctr.as<HwTileCounters>(), ctr)))
         return rc;
@@ -287,7 +284,7 @@ int hw_pairs_device_tiles(isocon_store *s, const uint32_t *q, const uint32_t *t,
         if (rc) return rc;
     }
     // ---- START + TRACE + walk for the hits ----
-    if ((rc = hw_device_tiles<1>(s, n_pairs, d_q.as<uint32_t>(), d_t.as<uint32_t>(), d_k.as<int32_t>(), d_he.as<int32_t>(), d_out.as<int32_t>(), d_key.as<uint32_t>(),
+    if ((rc = hw_device_tiles<1>(s, n_pairs, d_q, d_t, d_k, d_he.as<int32_t>(), d_out.as<int32_t>(), d_key.as<uint32_t>(),
                                  d_hist.as<uint32_t>(), d_cursor.as<uint32_t>(), d_tbase.as<uint32_t>(), n_keys, d_tq.as<uint32_t>(), d_lp.as<uint32_t>(), max_tiles,
                                  d_cls.as<uint32_t>(), d_ctr.as<HwTileCounters>(), ctr)))
         return rc;
@@ -316,9 +313,29 @@ int hw_pairs_device_tiles(isocon_store *s, const uint32_t *q, const uint32_t *t,
     clk.lap("hw: finish kernels");
     ISO_HIP_CHECK(hipMemcpy(&ctr, d_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost));
     if ((rc = flag_error(ctr.flags))) return rc;
-    ISO_HIP_CHECK(copy_d2h(out, d_out.p, n_pairs * 20));
-    clk.lap("hw: results down");
+    *d_rows = d_out.as<int32_t>();
     if (kernel_ms) *kernel_ms = tm.total;
+    return ISOCON_OK;
+}
+
+// Tiles built on the device: the caller's pair arrays go up once, the (n_pairs, 5) result comes down once.
+int hw_pairs_device_tiles(isocon_store *s, const uint32_t *q, const uint32_t *t, const int32_t *k, uint64_t n_pairs, int32_t *out, float *kernel_ms,
+                          bool *retry_host)
+{
+    *retry_host = false;
+    HostClock clk;
+    ScratchPool *pl = &g_scratch;
+    DevBuf d_q(pl, SLOT_HW_PQ), d_t(pl, SLOT_HW_T), d_k(pl, SLOT_HW_K);
+    int rc;
+    if ((rc = d_q.alloc(n_pairs * 4)) || (rc = d_t.alloc(n_pairs * 4)) || (rc = d_k.alloc(n_pairs * 4))) return rc;
+    ISO_HIP_CHECK(copy_h2d(d_q.p, q, n_pairs * 4));
+    ISO_HIP_CHECK(copy_h2d(d_t.p, t, n_pairs * 4));
+    ISO_HIP_CHECK(copy_h2d(d_k.p, k, n_pairs * 4));
+    clk.lap("hw: pair arrays up");
+    int32_t *d_rows = nullptr;
+    if ((rc = hw_pairs_device_core(s, d_q.as<uint32_t>(), d_t.as<uint32_t>(), d_k.as<int32_t>(), n_pairs, &d_rows, kernel_ms, retry_host))) return rc;
+    ISO_HIP_CHECK(copy_d2h(out, d_rows, n_pairs * 20));
+    clk.lap("hw: results down");
     return ISOCON_OK;
 }
 

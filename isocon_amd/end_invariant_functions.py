@@ -262,9 +262,47 @@ def _window_pairs(lens, q_lo, q_hi, window, depth):
     return np.asarray(qs, dtype=np.int64), np.asarray(ts, dtype=np.int64)
 
 
+# hw_window_graph is the fused form of THIS hw_pairs: a store class that brings its own (a stand-in without a GPU, an instrumented or
+# derived store) keeps the pair-list route, which calls it.
+_NATIVE_HW_PAIRS = SeqStore.hw_pairs
+
+
+def _device_window_graph(seq_to_acc_list_sorted, neighbor_search_depth, ignore_ends_threshold, symmetric):
+    """The graph of get_all_NN on the whole list (symmetric: the dict get_NN_graph_ignored_ends_edlib ends with) from one device call
+    (SeqStore.hw_window_graph: pairs, rows, end rules and edges on the device), or None where that call does not apply: a store class
+    without it or with a hw_pairs of its own, a list that is not length-sorted, a process group (the sharded pair-list route), a band
+    beyond 512 diagonals, the switch ISOCON_DEBUG_VARIANT=hw_host_graph, or a call that answers ISOCON_E_UNSUPPORTED / ISOCON_E_ARG."""
+    import os
+    from . import _lib
+    from .nearest_neighbor_graph import _process_group
+    max_variants = 10
+    max_ed_allowed = max_variants + ignore_ends_threshold
+    window = max_variants + 2 * ignore_ends_threshold
+    if not hasattr(SeqStore, "hw_window_graph") or getattr(SeqStore, "hw_pairs", None) is not _NATIVE_HW_PAIRS or window + 2 * max_ed_allowed + 1 > 512:
+        return None
+    if "hw_host_graph" in {item.split("=")[0] for item in os.environ.get("ISOCON_DEBUG_VARIANT", "").split(",")}:
+        return None
+    seqs = [s for s, _ in seq_to_acc_list_sorted]
+    accs = [a for _, a in seq_to_acc_list_sorted]
+    if any(len(seqs[i]) < len(seqs[i - 1]) for i in range(1, len(seqs))) or _process_group() is not None:
+        return None
+    try:
+        row_ptr, cols, ed = SeqStore(seqs).hw_window_graph(window, max_ed_allowed, neighbor_search_depth, ignore_ends_threshold, max_variants, symmetric)
+    except _lib.IsoconError as e:
+        if e.status in (_lib.ISOCON_E_UNSUPPORTED, _lib.ISOCON_E_ARG):
+            return None
+        raise
+    rp, cols, ed = row_ptr.tolist(), cols.tolist(), ed.tolist()
+    return {accs[i]: {accs[t]: d for t, d in zip(cols[rp[i]:rp[i + 1]], ed[rp[i]:rp[i + 1]])} for i in range(len(accs))}
+
+
 def get_all_NN(batch_of_queries, global_index_in_matrix, start_index, seq_to_acc_list_sorted, neighbor_search_depth, ignore_ends_threshold):
     """end_invariant_functions.py:622-681: {acc1: {acc2: ed}} for the queries start_index .. start_index + len(batch) of
     the (length-sorted) list against their length window; an edge is kept iff 0 <= ed <= 10 after the end adjustments."""
+    if start_index == 0 and len(batch_of_queries) == len(seq_to_acc_list_sorted):
+        graph = _device_window_graph(seq_to_acc_list_sorted, neighbor_search_depth, ignore_ends_threshold, False)
+        if graph is not None:
+            return graph
     max_variants = 10
     max_ed_allowed = max_variants + ignore_ends_threshold
     window = max_variants + 2 * ignore_ends_threshold
@@ -302,6 +340,10 @@ def get_NN_graph_ignored_ends_edlib(candidate_transcripts, args):
     position kept, stable sort by length), made symmetric with the smaller of the two directed values."""
     seq_to_acc = {seq: acc for (acc, seq) in candidate_transcripts.items()}
     seq_to_acc_list_sorted = sorted(seq_to_acc.items(), key=lambda x: len(x[0]))
+    all_neighbors_graph = _device_window_graph(seq_to_acc_list_sorted, args.neighbor_search_depth, args.ignore_ends_len, True)
+    if all_neighbors_graph is not None:                        # (symmetrised on the device, rows in the loop's insertion order)
+        assert len(candidate_transcripts) == len(all_neighbors_graph)
+        return all_neighbors_graph
     all_neighbors_graph = get_all_NN_under_ignored_edge_ends(seq_to_acc_list_sorted, args)
     for c1 in all_neighbors_graph:                             # the reference inserts while it iterates the inner dict of
         for c2 in list(all_neighbors_graph[c1]):               # c1 only when c2 == c1, which cannot happen

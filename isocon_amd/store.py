@@ -268,6 +268,42 @@ class SeqStore(object):
                                            _ptr(out, _lib.i32p), ctypes.byref(ms)), "isocon_hw_pairs")
         return (out, ms.value) if return_ms else out
 
+    def hw_window_graph(self, window, k, depth, end_threshold, max_ed, symmetric, return_counters=False):
+        """The candidate-vs-candidate graph with ignored ends of a length-sorted store in one call (isocon_hw_window_graph; reference
+        call sites end_invariant_functions.py:622-681, :593-620, :757-788): (row_ptr int64[n + 1], cols uint32[], ed int32[]) -- row i
+        holds the directed edges of entry i in the visit order of get_all_NN with their end-adjusted distances; symmetric: the smaller
+        of the two directions, then the entries that only point to i, in ascending position.  return_counters: a dict (pairs,
+        need_kernel, hits, directed, appended, kernel_ms) as fourth value.  Raises IsoconError (.status) like the other entries."""
+        n = self.n
+        row_ptr = np.zeros(n + 1, dtype=np.uint64)
+        # the ordered window pairs bound the edges: counted from the lengths (two searches per entry)
+        lens = self.lens
+        if n and bool((np.diff(lens) >= 0).all()):
+            jmax = max(1, int(min(depth, n)))
+            idx = np.arange(n, dtype=np.int64)
+            lo = np.maximum(np.searchsorted(lens, lens - int(window), side="left"), idx - jmax)
+            hi = np.minimum(np.searchsorted(lens, lens + int(window), side="right") - 1, idx + jmax)
+            cap = int((hi - lo).sum())
+        else:
+            cap = 0          # (an unsorted store is refused by the call)
+        cols = np.empty(max(cap, 1), dtype=np.uint32)
+        ed = np.empty(max(cap, 1), dtype=np.int32)
+        needed = ctypes.c_uint64(0)
+        counters = np.zeros(5, dtype=np.uint64)
+        ms = ctypes.c_float(0)
+        depth = int(min(max(int(depth), 0), 2 ** 64 - 1))
+        _lib.check(self._L.isocon_hw_window_graph(self._h, int(window), int(k), depth, int(end_threshold), int(max_ed), int(bool(symmetric)),
+                                                  _ptr(row_ptr, _lib.u64p), _ptr(cols, _lib.u32p), _ptr(ed, _lib.i32p), cap, ctypes.byref(needed),
+                                                  _ptr(counters, _lib.u64p), ctypes.byref(ms)), "isocon_hw_window_graph")
+        m = int(row_ptr[n])
+        out = (row_ptr.astype(np.int64), cols[:m], ed[:m])
+        if return_counters:
+            names = ("pairs", "need_kernel", "hits", "directed", "appended")
+            stats = {name: int(v) for name, v in zip(names, counters)}
+            stats["kernel_ms"] = ms.value
+            return out + (stats,)
+        return out
+
     # ---- nearest-neighbour graph (store must be length-sorted) ------------------------------------------------
     def nn_graph(self, is_converged=None, is_target=None, depth=2 ** 32):
         """Returns (best[n], row_ptr[n+1], cols, stats dict)."""
