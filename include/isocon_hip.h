@@ -427,6 +427,27 @@ int isocon_hw_window_graph(isocon_store *s, int32_t window, int32_t k, uint64_t 
                            uint64_t edges_cap, uint64_t *n_edges_needed, uint64_t *out_counters, float *kernel_ms);
 
 /*
+ * The invariance graph of the end-invariant collapse from the store alone: the pairs and the test of
+ * get_invariants_under_ignored_edge_ends_speed (modules/end_invariant_functions.py:920-951, is_overlap :884-918) on the device -- no
+ * sequence is compared on the host.  The store must be in ascending length order (ISOCON_E_ARG otherwise; so is thr < 0).
+ * Row i = out_cols[out_row_ptr[i] .. out_row_ptr[i + 1]): the positions p != i with len_i - 2 thr <= len_p <= len_i (equal lengths are
+ * visited from both sides) for which the reference's test of (seq1 = i, seq2 = p) holds, in ascending p:
+ *   p occurs inside i: its FIRST occurrence decides -- at most thr symbols of i before and after it -- and nothing else is tried;
+ *   otherwise a suffix of one equals a prefix of the other and leaves at most thr symbols of either uncovered.
+ * Both are "the two coincide on their whole overlap under one of at most 2 thr + 1 shifts" (csrc/end_inv_core.hpp): every shift of every
+ * window pair is screened on the first 64 bases of its overlap, the surviving (pair, shift) are verified over the whole overlap.
+ * Limits (ISOCON_E_UNSUPPORTED): a shortest sequence of at most thr symbols (the reference's test is then true for degenerate reasons:
+ * left to the host), thr > 1024, more than 0xfffffff0 window pairs or (pair, shift) survivors.  A store under its own map of at most
+ * four symbols works unchanged (only equality matters); one with more than four symbols returns ISOCON_E_ALPHABET, with the message of
+ * isocon_hw_pairs.  ISOCON_E_CAPACITY + *n_edges_needed when edges_cap is too small (out_row_ptr and the counters are valid then); the
+ * number of window pairs bounds the edges.
+ * out_counters (4 values, or NULL): window pairs, (pair, shift) survivors of the first-word test, pairs fully verified (those with a
+ * survivor), invariant pairs (= edges).  *kernel_ms sums the window, screening, verification and row kernels.
+ */
+int isocon_end_invariant_graph(isocon_store *s, int32_t thr, uint64_t *out_row_ptr /* n + 1 */, uint32_t *out_cols, uint64_t edges_cap,
+                               uint64_t *n_edges_needed, uint64_t *out_counters, float *kernel_ms);
+
+/*
  * edlib.align(q, t, mode="NW", task="path", k) for a pair list (modules/edlib_alignment_module.py:130-135 edlib_traceback).
  * k NULL or k[p] < 0: unbounded.  out_ed[p] = distance, or -1 above k (then the pair has no ops).  Pair p owns
  * out_ops[out_ops_ptr[p] .. out_ops_ptr[p + 1]), len << 4 | code (0 '=', 1 'X', 2 'I' query only, 3 'D' target only), forward order,

@@ -109,6 +109,7 @@ SYMBOLS = {
     "isocon_hw_pairs_wide": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, i32p, ctypes.c_uint64, i32p, f32p]),
     "isocon_hw_window_graph": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                               u64p, u32p, i32p, ctypes.c_uint64, u64p, u64p, f32p]),
+    "isocon_end_invariant_graph": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, u64p, u32p, ctypes.c_uint64, u64p, u64p, f32p]),
     "isocon_ed_path_pairs": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, i32p, ctypes.c_uint64, i32p, u32p, u64p, ctypes.c_uint64, u64p, f32p]),
     "isocon_hw_path_pairs": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, i32p, ctypes.c_uint64, i32p, u32p, u64p, ctypes.c_uint64, u64p, f32p]),
     "isocon_readtab_create": (ctypes.c_int, [u8p, u8p, u64p, ctypes.c_uint32, u32p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p), u32p, f32p]),

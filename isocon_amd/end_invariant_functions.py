@@ -3,8 +3,9 @@ the read-to-candidate alignment of find_candidate_transcripts).
 
 Mirror of /root/reference/modules/end_invariant_functions.py:884-918 (`is_overlap`), :920-951
 (`get_invariants_under_ignored_edge_ends_speed`), :405-533 (`partition_highest_reachable_with_edge_degrees`) and
-:975-1065 (`collapse_candidates_under_ends_invariant`).  Pure string work on the (few thousand) candidates -- exact
-substring / suffix-prefix tests, no alignment -- so it stays on the host, like in the reference.
+:975-1065 (`collapse_candidates_under_ends_invariant`).  Exact substring / suffix-prefix tests, no alignment: with a GPU
+the invariance graph comes from one device call that tests every shift of every window pair on the bit planes
+(isocon_end_invariant_graph, csrc/end_inv.hpp); the string route on the host stays as fallback and comparator.
 
 Second part: the candidate-vs-candidate graph of the statistical-test phase --
 `edlib_traceback` (:593-620, edlib HW mode + path), `get_all_NN` (:622-681), `get_all_NN_under_ignored_edge_ends`
@@ -85,12 +86,62 @@ def _shift_consistent(A, B, thr, K=24):
     return False
 
 
+# Which route built the invariance graphs: device_calls -- graphs whose rows came from isocon_end_invariant_graph --, the window pairs and
+# directed rows entries of those calls, and their kernel time.
+INVARIANT_STATS = {"device_calls": 0, "pairs": 0, "edges": 0, "kernel_ms": 0.0}
+_HAS_DEVICE = None
+
+
+def _device_invariant_rows(seqs, thr):
+    """Rows of the invariance graph of the length-sorted list `seqs` from one device call (SeqStore.end_invariant_graph: windows, the test
+    of every pair and the rows on the device): (row_ptr, cols, counters) as lists / a dict, row i = the partners p of the host loop's
+    entry i, ascending.  None where that call does not apply: no library or no GPU, a store class without the method, the switch
+    ISOCON_DEBUG_VARIANT=inv_host_graph, sequences that are not plain ASCII str, or a call that answers ISOCON_E_UNSUPPORTED (a
+    sequence of at most thr symbols, thr beyond the limit), ISOCON_E_ARG or ISOCON_E_ALPHABET (more than four symbols)."""
+    global _HAS_DEVICE
+    import os
+    from . import _lib
+    if not hasattr(SeqStore, "end_invariant_graph") or not seqs:
+        return None
+    if "inv_host_graph" in {item.split("=")[0] for item in os.environ.get("ISOCON_DEBUG_VARIANT", "").split(",")}:
+        return None
+    if not all(type(s) is str and s.isascii() for s in seqs):
+        return None
+    if _HAS_DEVICE is None:
+        try:
+            _HAS_DEVICE = _lib.load().isocon_device_count() > 0
+        except (RuntimeError, OSError):          # (no library)
+            _HAS_DEVICE = False
+    if not _HAS_DEVICE:
+        return None
+    store = None
+    try:
+        store = SeqStore(seqs)
+        row_ptr, cols, counters, ms = store.end_invariant_graph(thr, return_counters=True)
+    except _lib.IsoconError as e:
+        if e.status in (_lib.ISOCON_E_UNSUPPORTED, _lib.ISOCON_E_ARG, _lib.ISOCON_E_ALPHABET):
+            return None
+        raise
+    finally:
+        if store is not None:
+            store.close()
+    INVARIANT_STATS["device_calls"] += 1
+    INVARIANT_STATS["pairs"] += counters["pairs"]
+    INVARIANT_STATS["edges"] += len(cols)
+    INVARIANT_STATS["kernel_ms"] += ms
+    return row_ptr.tolist(), cols.tolist(), counters
+
+
 def get_invariants_under_ignored_edge_ends_speed(candidate_transcripts, candidate_support, params):
     """:920-951.  DiGraph on candidate accessions (node attribute `degree` = support) with edges in both directions
     between candidates of which one is contained in the other, or which overlap suffix-to-prefix, leaving at most
     params.ignore_ends_len characters at either end.
 
-    The reference tests every pair inside the length window (quadratic in the candidates).  Here pairs are proposed by an
+    The reference tests every pair inside the length window (quadratic in the candidates).  With a GPU that is what happens, on the
+    device: one call tests every shift of every window pair on the bit planes and returns the rows (_device_invariant_rows;
+    INVARIANT_STATS counts these calls).  Under a process group every rank makes that call itself: it is deterministic and cheap.
+
+    Without one -- or where the call does not apply -- pairs are proposed by an
     anchor index first: whichever of the three relations holds, the K-mer at offset thr of one string occurs in the
     other at an offset in [thr, 2 thr] (the strings coincide up to a shift of at most thr; K = shortest length - 3 thr),
     so only pairs sharing such a K-mer are tested -- with the reference's own test.  Sets with a very short candidate take the quadratic route."""
@@ -98,14 +149,25 @@ def get_invariants_under_ignored_edge_ends_speed(candidate_transcripts, candidat
 
     import networkx as nx
     from . import _lib
-    H = _lib.pyhelp()
-    if H is not None and not hasattr(H, "invariant_partners"):
-        H = None
     thr = params.ignore_ends_len
     G = nx.DiGraph()
     for acc in candidate_transcripts:
         G.add_node(acc, degree=candidate_support[acc])
     by_len = sorted(candidate_transcripts.items(), key=lambda x: len(x[1]))
+    rows = _device_invariant_rows([s for _, s in by_len], thr)
+    if rows is not None:
+        # the host loop's insertion order: i ascending in the stable length sort, p ascending in row i
+        row_ptr, cols, _ = rows
+        accs = [acc for acc, _ in by_len]
+        for i, acc1 in enumerate(accs):
+            for p in cols[row_ptr[i]:row_ptr[i + 1]]:
+                acc2 = accs[p]
+                G.add_edge(acc2, acc1)
+                G.add_edge(acc1, acc2)
+        return G
+    H = _lib.pyhelp()
+    if H is not None and not hasattr(H, "invariant_partners"):
+        H = None
     lens = [len(s) for _, s in by_len]
     pos_of = {acc: i for i, (acc, _) in enumerate(by_len)}
     # anchor length: as long as the shortest candidate allows (related strings are IDENTICAL on their whole overlap, so a

@@ -304,6 +304,32 @@ class SeqStore(object):
             return out + (stats,)
         return out
 
+    def end_invariant_graph(self, thr, return_counters=False):
+        """The invariance graph of the end-invariant collapse of a length-sorted store in one call (isocon_end_invariant_graph; reference
+        call site end_invariant_functions.py:920-951): (row_ptr int64[n + 1], cols uint32[]) -- row i holds, in ascending position, the
+        entries p != i with len_i - 2 thr <= len_p <= len_i that are contained in i or overlap it suffix-to-prefix leaving at most thr
+        symbols at either end (the reference's test of the ordered pair).  return_counters: a dict (pairs, survivors, verified,
+        invariant) and the kernel time in ms as third and fourth value.  Raises IsoconError (.status) like the other entries."""
+        n = self.n
+        row_ptr = np.zeros(n + 1, dtype=np.uint64)
+        needed = ctypes.c_uint64(0)
+        counters = np.zeros(4, dtype=np.uint64)
+        ms = ctypes.c_float(0)
+        cap = max(4 * n, 1024)
+        for attempt in (0, 1):          # (the capacity grows once: the call states what it needs)
+            cols = np.empty(cap, dtype=np.uint32)
+            rc = self._L.isocon_end_invariant_graph(self._h, int(thr), _ptr(row_ptr, _lib.u64p), _ptr(cols, _lib.u32p), cap, ctypes.byref(needed),
+                                                    _ptr(counters, _lib.u64p), ctypes.byref(ms))
+            if rc == _lib.ISOCON_E_CAPACITY and attempt == 0:
+                cap = int(needed.value)
+                continue
+            _lib.check(rc, "isocon_end_invariant_graph")
+            break
+        out = (row_ptr.astype(np.int64), cols[:int(row_ptr[n])])
+        if return_counters:
+            return out + ({name: int(v) for name, v in zip(("pairs", "survivors", "verified", "invariant"), counters)}, ms.value)
+        return out
+
     # ---- nearest-neighbour graph (store must be length-sorted) ------------------------------------------------
     def nn_graph(self, is_converged=None, is_target=None, depth=2 ** 32):
         """Returns (best[n], row_ptr[n+1], cols, stats dict)."""
