@@ -93,17 +93,45 @@ __device__ __forceinline__ uint32_t nn_meta_score(uint32_t w) { return w >> 23; 
 static constexpr uint32_t NN_META_PAD = 3;          // words behind the last entry's, all 0 (no roles: never a candidate): the scan loads four words at once
 typedef uint32_t NNMeta4 __attribute__((ext_vector_type(4), aligned(4)));          // four meta words of consecutive entries: one 16-byte load at a dword address
 
-__global__ __launch_bounds__(256) void k_nn_entry_meta(DevStore S, NNParams P, const uint32_t *__restrict__ score, uint32_t *__restrict__ meta, NNPlanTotals *__restrict__ totals)
+// The same facts as the packed test of the scan wants them (nn_surv_core.hpp surv_test4: four partners per instruction), an item per entry
+// in three arrays behind the meta words, each with the NN_META_PAD items of padding (no roles, guard bits set).  A lane loads the items
+// of its four partners with one load per array, at any byte address.
+struct NNSurvSide {
+    const uint8_t *role, *len7;          // surv_role_byte (the cap of the pass folded in), surv_len_byte
+    const uint16_t *score;               // surv_score_half
+};
+// the packed test needs every threshold + 1 in seven bits (and a length-sorted store: every caller's), and has no third class
+static inline bool nn_surv_packed(int32_t kcap, int32_t class_mode) { return class_mode <= 0 && kcap >= 0 && kcap <= 63; }
+static inline size_t nn_meta_bytes(size_t n) { return (n + NN_META_PAD) * 8; }          // meta words, score halves, role bytes, length bytes
+static inline NNSurvSide nn_surv_side(uint32_t *meta, size_t n)
+{
+    NNSurvSide s;
+    uint16_t *sc = reinterpret_cast<uint16_t *>(meta + (n + NN_META_PAD));
+    uint8_t *role = reinterpret_cast<uint8_t *>(sc + (n + NN_META_PAD));
+    s.score = sc; s.role = role; s.len7 = role + (n + NN_META_PAD);
+    return s;
+}
+
+__global__ __launch_bounds__(256) void k_nn_entry_meta(DevStore S, NNParams P, const uint32_t *__restrict__ score, uint32_t *__restrict__ meta, NNSurvSide A, NNPlanTotals *__restrict__ totals)
 {
     const uint32_t x = blockIdx.x * 256u + threadIdx.x;
-    if (x >= S.n && x < S.n + NN_META_PAD) meta[x] = 0u;
+    if (x >= S.n && x < S.n + NN_META_PAD) {
+        meta[x] = 0u;
+        const_cast<uint8_t *>(A.role)[x] = 0;
+        const_cast<uint8_t *>(A.len7)[x] = surv_len_byte(0);
+        const_cast<uint16_t *>(A.score)[x] = surv_score_half(0);
+    }
     if (x < S.n) {
         const int32_t m = S.lens[x], b = load_relaxed_agent(P.best + x);
         int32_t thr = b < m ? b : m;
         thr = thr < 64 ? thr : 64;
         const uint32_t sc = score[x] >> 5;
-        const bool isq = P.qflag[x] != 0;
-        meta[x] = ((uint32_t)m & 0x3fffu) | ((uint32_t)thr << 14) | ((P.tflag[x] != 0 ? 1u : 0u) << 21) | ((isq ? 1u : 0u) << 22) | ((sc < 511u ? sc : 511u) << 23);
+        const bool isq = P.qflag[x] != 0, ist = P.tflag[x] != 0;
+        const uint32_t sc9 = sc < 511u ? sc : 511u;
+        meta[x] = ((uint32_t)m & 0x3fffu) | ((uint32_t)thr << 14) | ((ist ? 1u : 0u) << 21) | ((isq ? 1u : 0u) << 22) | (sc9 << 23);
+        const_cast<uint8_t *>(A.role)[x] = surv_role_byte(ist, isq, thr, P.kcap);
+        const_cast<uint8_t *>(A.len7)[x] = surv_len_byte((uint32_t)m);
+        const_cast<uint16_t *>(A.score)[x] = surv_score_half(sc9);
     }
 }
 
@@ -113,7 +141,8 @@ __global__ __launch_bounds__(256) void k_nn_entry_meta(DevStore S, NNParams P, c
 // surviving pair is kept by exactly one of its two ends.  Kept pairs are staged in LDS; NN_LIST_CHUNK staged pairs become a chunk
 // of `list` (one k_nn_scan_refill workgroup with x's table), what is left at the end becomes a last chunk if it has NN_LIST_MIN
 // pairs, else flat pairs for the one-pair-per-lane kernel -- those of them that the seed pass has not settled (K).
-__global__ __launch_bounds__(64 * NN_SURV_WAVES) void k_nn_survivors(DevStore S, NNParams P, NNBoundRows B, const uint32_t *__restrict__ meta, QMap Q, uint32_t nq,
+template <bool PACKED>
+__global__ __launch_bounds__(64 * NN_SURV_WAVES) void k_nn_survivors(DevStore S, NNParams P, NNBoundRows B, const uint32_t *__restrict__ meta, NNSurvSide A, QMap Q, uint32_t nq,
                                                        uint32_t *__restrict__ list, unsigned long long list_cap, NNChunk *__restrict__ chunks, unsigned long long chunks_cap,
                                                        uint32_t *__restrict__ pa, uint32_t *__restrict__ pb, unsigned long long small_cap, NNPlanTotals *__restrict__ totals, uint32_t list_min,
                                                        int32_t class_mode, NNSeedKnown K)
@@ -136,6 +165,13 @@ __global__ __launch_bounds__(64 * NN_SURV_WAVES) void k_nn_survivors(DevStore S,
             up_off = B.row_off[s];
         }
         dn_len = B.lenT[x]; dn_slo = B.sloT[x]; dn_off = B.offT[x];
+    }
+    if constexpr (PACKED && NN_SURV_WAVES == 1) {
+        // (one entry per wave: what describes its rows is wave-uniform, and the loops over them are scalar when the compiler knows it)
+        const auto uni = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+        up_len = uni(up_len); dn_len = uni(dn_len); dn_slo = uni(dn_slo);
+        up_off = ((unsigned long long)uni((uint32_t)(up_off >> 32)) << 32) | uni((uint32_t)up_off);
+        dn_off = ((unsigned long long)uni((uint32_t)(dn_off >> 32)) << 32) | uni((uint32_t)dn_off);
     }
     const int32_t m = (int32_t)nn_meta_len(mx);
     const int32_t kx0 = nn_meta_thr(mx);
@@ -173,6 +209,24 @@ __global__ __launch_bounds__(64 * NN_SURV_WAVES) void k_nn_survivors(DevStore S,
     const uint32_t role_mask = (x_isq ? 1u << 21 : 0u) | (x_ist ? 1u << 22 : 0u);          // the role bits of a partner that make a direction of the pair
     // Q.entry() modulo 2^32 (entries are below 2^30)
     auto entry_of = [&](uint32_t s) { return Q.begin + (s >> Q.block_log2) * Q.stride + (s & (q_block - 1u)); };
+    // the kept pairs of a batch into the staging buffer, by their keep masks; word(b): the list word of the lane's pair b
+    auto stage_batch = [&](const uint64_t (&am)[SURV_PER_LANE], const uint64_t (&an)[SURV_PER_LANE], auto word) {
+        fill = (uint32_t)__builtin_amdgcn_readfirstlane((int)fill);          // (wave-uniform, and the compiler should know it)
+        fill_n = (uint32_t)__builtin_amdgcn_readfirstlane((int)fill_n);
+        surv_batch(am, an, fill, fill_n, NN_LIST_CHUNK,
+                   [&](uint64_t lanes, uint32_t off_a, uint32_t off_n) {
+                       if (surv_lane_bit(lanes, lane) == 0) return;
+                       uint32_t at_a = off_a + surv_rank(am, lane), at_n = (uint32_t)NN_STAGE - 1u - (off_n + surv_rank(an, lane));
+#pragma unroll
+                       for (int b = 0; b < SURV_PER_LANE; ++b) {
+                           const uint32_t ka = surv_lane_bit(am[b], lane), kn = surv_lane_bit(an[b], lane);
+                           if (ka | kn) st[ka ? at_a : at_n] = word(b);
+                           at_a += ka;
+                           at_n -= kn;
+                       }
+                   },
+                   [&](bool narrow_class) { emit_chunk(narrow_class); });          // the buffer is full: its larger class leaves (>= half a chunk)
+    };
     // (the side is a compile-time constant of the loop body: own row = contiguous partners, transposed row = partners through the slot map)
     auto scan_side = [&](auto side_tag) {
         constexpr int side = decltype(side_tag)::value;
@@ -210,28 +264,13 @@ __global__ __launch_bounds__(64 * NN_SURV_WAVES) void k_nn_survivors(DevStore S,
 #pragma unroll
                 for (int b = 0; b < SURV_PER_LANE; ++b) {
                     const uint32_t myb = my[u][b];
-                    const bool inr = e0 + b < len;
-                    const bool xq = inr && x_isq && (myb & (1u << 21));        // x queries y
-                    const bool yq = inr && x_ist && (myb & (1u << 22));        // y queries x
-                    int32_t kx = -1, ky = -1;
-                    if (xq) kx = kx0;
-                    if (yq) ky = nn_meta_thr(myb);
-                    int32_t k = kx > ky ? kx : ky;
-                    if (k > P.kcap) k = P.kcap;
-                    const int32_t dl = m - (int32_t)nn_meta_len(myb), ad = dl < 0 ? -dl : dl;
-                    const uint32_t sy_u = nn_meta_score(myb);
-                    const bool cand = inr && k >= 0 && ad <= k;
-                    const bool accept = cand && (int32_t)((lbv[u] >> (8 * b)) & 0xffu) <= k;
-                    // owner: larger hub score, ties to the lower index (side 0: x is the lower end)
-                    const bool mine = accept && (side == 0 ? sy_u <= sx : sx > sy_u);
-                    if (side == 0) { filtered += cand && !accept ? 1u : 0u; kept += accept ? 1u : 0u; }          // (per lane: summed once per entry)
+                    const SurvTest t = surv_test(e0 + b < len, x_isq, x_ist, (myb & (1u << 22)) != 0, (myb & (1u << 21)) != 0, kx0, nn_meta_thr(myb), P.kcap, m, (int32_t)nn_meta_len(myb),
+                                                 (lbv[u] >> (8 * b)) & 0xffu, sx, nn_meta_score(myb), side, class_mode);
+                    if (side == 0) { filtered += t.cand && !t.accept ? 1u : 0u; kept += t.accept ? 1u : 0u; }          // (per lane: summed once per entry)
                     // class mode +1: the pairs with a threshold above the 32-row form's go straight to the pair arrays
-                    const bool wide = mine && class_mode > 0 && k > NN_NARROW_K;
-                    const bool keep = mine && !wide;
-                    const bool to_narrow = keep && class_mode >= 0 && k <= NN_NARROW_K;
-                    aw[b] = __builtin_amdgcn_ballot_w64(wide);
-                    am[b] = __builtin_amdgcn_ballot_w64(keep && !to_narrow);
-                    an[b] = __builtin_amdgcn_ballot_w64(to_narrow);
+                    aw[b] = __builtin_amdgcn_ballot_w64(t.wide);
+                    am[b] = __builtin_amdgcn_ballot_w64(t.keep && !t.to_narrow);
+                    an[b] = __builtin_amdgcn_ballot_w64(t.to_narrow);
                 }
                 // (what a kept pair needs beyond its mask bit is made where it is stored: most batches keep nothing)
                 // the list word of pair b: partner | x queries y << 30 | y queries x << 31 (a kept pair is in range: its role bits are the meta word's)
@@ -260,21 +299,7 @@ __global__ __launch_bounds__(64 * NN_SURV_WAVES) void k_nn_survivors(DevStore S,
                         }
                     }
                 }
-                fill = (uint32_t)__builtin_amdgcn_readfirstlane((int)fill);          // (wave-uniform, and the compiler should know it)
-                fill_n = (uint32_t)__builtin_amdgcn_readfirstlane((int)fill_n);
-                surv_batch(am, an, fill, fill_n, NN_LIST_CHUNK,
-                           [&](uint64_t lanes, uint32_t off_a, uint32_t off_n) {
-                               if (surv_lane_bit(lanes, lane) == 0) return;
-                               uint32_t at_a = off_a + surv_rank(am, lane), at_n = (uint32_t)NN_STAGE - 1u - (off_n + surv_rank(an, lane));
-#pragma unroll
-                               for (int b = 0; b < SURV_PER_LANE; ++b) {
-                                   const uint32_t ka = surv_lane_bit(am[b], lane), kn = surv_lane_bit(an[b], lane);
-                                   if (ka | kn) st[ka ? at_a : at_n] = word(b);
-                                   at_a += ka;
-                                   at_n -= kn;
-                               }
-                           },
-                           [&](bool narrow_class) { emit_chunk(narrow_class); });          // the buffer is full: its larger class leaves (>= half a chunk)
+                stage_batch(am, an, word);
             }
         };
         for (uint32_t c0 = 0; c0 < len; c0 += SURV_BATCH * U) {
@@ -284,8 +309,96 @@ __global__ __launch_bounds__(64 * NN_SURV_WAVES) void k_nn_survivors(DevStore S,
             scan_batches(c0, lbv, my);
         }
     };
-    scan_side(std::integral_constant<int, 0>());
-    scan_side(std::integral_constant<int, 1>());
+    // The same scan with the test on a lane's four pairs at once (nn_surv_core.hpp surv_test4): the partners' items come from the three
+    // arrays of NNSurvSide, the keep masks as a bit per byte, and the ballots are only formed for a batch that keeps a pair at all.
+    // Iterations whose U batches lie inside the row (full_tag) address by lane alone and mask nothing.
+    uint32_t ncand_p = 0, kept_p = 0;          // candidates / accepted pairs of side 0 (per lane)
+    auto scan_side_packed = [&](auto side_tag) {
+        constexpr int side = decltype(side_tag)::value;
+        const uint32_t len = side == 0 ? up_len : dn_len;
+        const uint8_t *row = side == 0 ? B.lb + up_off : B.lbT + dn_off;
+        const uint32_t tail = (len - 1u) & ~3u;
+        const SurvX X = surv_x(x_isq, x_ist, kx0, P.kcap, m, sx, side, class_mode);
+        const bool blocks_apart = side != 0 && Q.stride != q_block;          // (wave-uniform) consecutive slots need not be consecutive entries
+        auto iteration = [&](uint32_t c0, auto full_tag) {
+            constexpr bool full = decltype(full_tag)::value;
+            uint32_t lbv[U], role[U], len7[U];
+            uint2 sc[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const uint32_t e0 = c0 + (uint32_t)SURV_BATCH * u + 4u * (uint32_t)lane;
+                const uint32_t ec = full || e0 < len ? e0 : tail;
+                __builtin_memcpy(&lbv[u], row + ec, 4);
+                const uint32_t y0 = side == 0 ? x + 1u + ec : entry_of(dn_slo + ec);
+                const bool apart = blocks_apart && ((dn_slo + ec) & (q_block - 1u)) + 3u >= q_block;
+                if (!blocks_apart || __builtin_amdgcn_ballot_w64(apart) == 0) {
+                    __builtin_memcpy(&role[u], A.role + y0, 4);
+                    __builtin_memcpy(&len7[u], A.len7 + y0, 4);
+                    __builtin_memcpy(&sc[u], A.score + y0, 8);
+                } else {
+                    // a lane's four slots cross a block of the map: their items one by one (the slots behind the row's end read its last one)
+                    role[u] = len7[u] = 0u;
+                    sc[u] = make_uint2(0u, 0u);
+#pragma unroll
+                    for (int b = 0; b < SURV_PER_LANE; ++b) {
+                        const uint32_t y = entry_of(dn_slo + (ec + b < len ? ec + b : len - 1u));
+                        role[u] |= (uint32_t)A.role[y] << (8 * b);
+                        len7[u] |= (uint32_t)A.len7[y] << (8 * b);
+                        if (b < 2) sc[u].x |= (uint32_t)A.score[y] << (16 * b);
+                        else sc[u].y |= (uint32_t)A.score[y] << (16 * (b - 2));
+                    }
+                }
+            }
+            // (a batch behind the row's end has no position inside it: it tests nothing true and keeps nothing)
+            uint32_t keep[U], any = 0u;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const uint32_t e0 = c0 + (uint32_t)SURV_BATCH * u + 4u * (uint32_t)lane;
+                if (!full) role[u] &= surv_inr_bytes((int32_t)len - (int32_t)e0);          // (e0 and len are below 2^31)
+                uint32_t cand, accept;
+                surv_test4<side>(X, lbv[u], role[u], len7[u], sc[u].x, sc[u].y, cand, accept, keep[u]);
+                if (side == 0) { ncand_p += (uint32_t)__popc(cand); kept_p += (uint32_t)__popc(accept); }
+                any |= keep[u];
+            }
+            if (__builtin_amdgcn_ballot_w64(any != 0u) == 0) return;                             // wave-uniform: most iterations keep nothing
+            // the ballots and the stores of the batches that keep a pair, one batch after the other (one copy of the code)
+#pragma unroll 1
+            for (int u = 0; u < U; ++u) {
+                uint32_t keep_u = keep[0], role_u = role[0];
+#pragma unroll
+                for (int v = 1; v < U; ++v) { keep_u = u == v ? keep[v] : keep_u; role_u = u == v ? role[v] : role_u; }
+                if (__builtin_amdgcn_ballot_w64(keep_u != 0u) == 0) continue;
+                const uint32_t e0 = c0 + (uint32_t)SURV_BATCH * (uint32_t)u + 4u * (uint32_t)lane;
+                const uint32_t kn = keep_u & surv_narrow4(X, role_u), ka = keep_u & ~kn;
+                uint64_t am[SURV_PER_LANE], an[SURV_PER_LANE];
+#pragma unroll
+                for (int b = 0; b < SURV_PER_LANE; ++b) {
+                    am[b] = __builtin_amdgcn_ballot_w64((ka & (0x80u << (8 * b))) != 0u);
+                    an[b] = __builtin_amdgcn_ballot_w64((kn & (0x80u << (8 * b))) != 0u);
+                }
+                // the list word of pair b (as above): the partner is a target -> x queries y, the partner queries (its b is not 0) -> y queries x
+                const auto word = [&](int b) {
+                    const uint32_t y = side == 0 ? x + 1u + e0 + (uint32_t)b : entry_of(dn_slo + e0 + (uint32_t)b);
+                    const uint32_t rb = role_u >> (8 * b);
+                    return y | (x_isq && (rb & 0x80u) ? 1u << 30 : 0u) | (x_ist && (rb & 0x7fu) ? 1u << 31 : 0u);
+                };
+                stage_batch(am, an, word);
+            }
+        };
+        uint32_t c0 = 0;
+        for (; c0 + (uint32_t)(SURV_BATCH * U) <= len; c0 += SURV_BATCH * U) iteration(c0, std::true_type());
+        if (c0 < len) iteration(c0, std::false_type());
+    };
+    // (the host instantiates the packed form where every threshold + 1 fits seven bits and there is no third class: nn_surv_packed)
+    if constexpr (PACKED) {
+        scan_side_packed(std::integral_constant<int, 0>());
+        scan_side_packed(std::integral_constant<int, 1>());
+        filtered += ncand_p - kept_p;
+        kept += kept_p;
+    } else {
+        scan_side(std::integral_constant<int, 0>());
+        scan_side(std::integral_constant<int, 1>());
+    }
     // the end of the entry's pairs: a class with enough pairs leaves as a chunk of its own; too few of the 32-row class join the 64-row
     // class (its kernel takes any threshold) before that class is judged
     if (fill_n >= list_min) emit_chunk(true);

@@ -26,7 +26,7 @@ int NNContext::plan_lists(const QMap &Q, uint32_t nq, const NNParams &PR, ListPl
     const unsigned long long tasks_cap = second ? 2 * cap_in + pairs_cap / 64 + 1 : 0;
     if (second && d_ltasks.alloc((size_t)tasks_cap * sizeof(NNFTask))) return ISOCON_OK;
     const size_t n_records = (size_t)(filter ? 2 * cap_in : 0) + 4 * (size_t)cap_out;
-    if (d_lmeta.alloc(((size_t)n + NN_META_PAD) * 4) || d_ltot.alloc(sizeof(NNPlanTotals)) || d_lchunks.alloc(n_records * sizeof(NNChunk)) || d_list.alloc((size_t)pairs_cap * 4) ||
+    if (d_lmeta.alloc(nn_meta_bytes(n)) || d_ltot.alloc(sizeof(NNPlanTotals)) || d_lchunks.alloc(n_records * sizeof(NNChunk)) || d_list.alloc((size_t)pairs_cap * 4) ||
         d_lpa.alloc((size_t)pairs_cap * 4) || d_lpb.alloc((size_t)pairs_cap * 4))
         return ISOCON_OK;
     // [builder: a, b (cap_in each; only with the filter)] [a, b as the alignment launches get them (cap_out each)] [their sorted copies]
@@ -47,9 +47,12 @@ int NNContext::plan_lists(const QMap &Q, uint32_t nq, const NNParams &PR, ListPl
     tm.start();
     int32_t class_mode = 0;          // variant nn_narrow=0: every pair on 64 rows; =1: pairs above 31 leave the lists for the pair-per-lane kernel (nn_list.hpp)
     if (const char *e = variant_value("nn_narrow")) class_mode = atoi(e) > 0 ? 1 : -1;
-    hipLaunchKernelGGL(k_nn_entry_meta, dim3((n + NN_META_PAD + 255) / 256), dim3(256), 0, 0, st->dev, PR, B.score, d_lmeta.as<uint32_t>(), d_ltot.as<NNPlanTotals>());
+    const NNSurvSide side = nn_surv_side(d_lmeta.as<uint32_t>(), n);          // the partners' items for the packed test, behind the meta words
+    // four pairs per instruction, or pair by pair (variant nn_surv_scalar: A/B runs, tests)
+    auto *const survivors = nn_surv_packed(PR.kcap, class_mode) && !variant("nn_surv_scalar") ? k_nn_survivors<true> : k_nn_survivors<false>;
+    hipLaunchKernelGGL(k_nn_entry_meta, dim3((n + NN_META_PAD + 255) / 256), dim3(256), 0, 0, st->dev, PR, B.score, d_lmeta.as<uint32_t>(), side, d_ltot.as<NNPlanTotals>());
     ISO_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_nn_survivors, dim3((n + NN_SURV_WAVES - 1) / NN_SURV_WAVES), dim3(64 * NN_SURV_WAVES), 0, 0, st->dev, PR, B, d_lmeta.as<uint32_t>(), Q, nq, d_list.as<uint32_t>(), pairs_cap,
+    hipLaunchKernelGGL(survivors, dim3((n + NN_SURV_WAVES - 1) / NN_SURV_WAVES), dim3(64 * NN_SURV_WAVES), 0, 0, st->dev, PR, B, d_lmeta.as<uint32_t>(), side, Q, nq, d_list.as<uint32_t>(), pairs_cap,
                        filter ? built : L.a, cap_in, d_lpa.as<uint32_t>(), d_lpb.as<uint32_t>(), pairs_cap, d_ltot.as<NNPlanTotals>(), build_min, class_mode, K);
     ISO_HIP_CHECK(hipGetLastError());
     if (filter) {
