@@ -1,8 +1,14 @@
 // ed_lanes.hpp -- banded bit-vector edit distance with ONE PAIR PER LANE (64-row band, thresholds up to 63): nothing is shared
 // between the lanes of a wave, so a list of unrelated pairs keeps all 64 lanes busy (the tile kernels of ed_band.hpp / nn.hpp
-// want 64 partners of one shared sequence).  Same band math (band_core.hpp); the pattern window of a lane is cut out of
-// 96-bit registers that hold its bit-planes for the 32 columns of a block (two v_alignbit per plane and column), the text
-// base of a column is a sign-extended 1-bit field of the lane's own text words.
+// want 64 partners of one shared sequence).  Same band math (band_core.hpp); a lane holds the bit-planes of its pattern for the
+// 32 columns of a block in 96-bit registers.  In a block of 32 full columns without virtual rows the lane turns them once into
+// the four match masks of the 96 positions, one per base, and keeps them in 64 bytes of LDS of its own; a column's match
+// vector then is one 16-byte LDS read, picked by the column's text base and requested four columns ahead, and two v_alignbit
+// (ed_lanes_core.hpp EqFromTable: 4 instructions and a read per column where cutting both planes out of the registers and
+// comparing them with the splat text bits took 10).  First blocks and text tails keep the register form.
+//
+// LDS: 16 bytes x 4 bases x 64 lanes = 4 KB per wave, 16 KB per workgroup (static), so the 8 workgroups of 4 waves that the
+// registers allow on a CU take 128 of its 160 KB.  No barrier anywhere: a lane reads only what it wrote.
 //
 // Used by the nearest-neighbour search to turn the smallest q-gram bounds of every entry into exact distances before the
 // main pass starts (tight thresholds from the first pair on), replacing edlib.align(x, y, "NW", "distance", k)
@@ -61,7 +67,10 @@ __global__ __launch_bounds__(256) void k_ed_lanes(DevStore S, NNParams P, const 
     auto x_hi = [&](int32_t ci) -> uint64_t { return ci < nchunks ? planes[((size_t)ci * nseq + x) * 2 + 1] : 0; };
     auto y_lo = [&](int32_t ci) -> uint64_t { return ci < nchunks ? planes[((size_t)ci * nseq + y) * 2] : 0; };
     auto y_hi = [&](int32_t ci) -> uint64_t { return ci < nchunks ? planes[((size_t)ci * nseq + y) * 2 + 1] : 0; };
-    const int32_t rd = lane_pair_distance(x_lo, x_hi, y_lo, y_hi, m, n, k, run, [](bool b) { return __ballot(b) != 0; });
+    // the lanes' match-mask slots (EqFromTable): 4 KB per wave, [wave][base][lane]
+    __shared__ eq_rec_t eq_tab[4 * EQ_TABLE_RECS];
+    const EqFromTable eq(eq_tab, threadIdx.x >> 6, threadIdx.x & 63u);
+    const int32_t rd = lane_pair_distance(x_lo, x_hi, y_lo, y_hi, m, n, k, run, [](bool b) { return __ballot(b) != 0; }, eq);
     if (run) r = rd;
     if (!NN) {
         if (i < n_pairs) out[i] = r;
