@@ -22,6 +22,7 @@
 #include "nn_finalize.hpp"
 #include "nn_finalize_host.hpp"
 #include "partition_host.hpp"
+#include "ed_pairs_plan.hpp"
 #include "sg.hpp"
 #include "msa.hpp"
 #include "hw.hpp"
@@ -320,6 +321,13 @@ struct DevBuf {
         ISO_HIP_CHECK(hipMalloc(&p, bytes ? bytes : 16));
         return ISOCON_OK;
     }
+    // alloc + the host array's copy up
+    int upload(const void *src, size_t bytes)
+    {
+        if (int rc = alloc(bytes)) return rc;
+        ISO_HIP_CHECK(copy_h2d(p, src, bytes));
+        return ISOCON_OK;
+    }
 };
 
 // out[0 .. n] = exclusive prefix sums of f(in[i]) (common.hpp: k_scan_tiles + k_scan_finish), on `stream`.  A scan on another stream than
@@ -479,6 +487,137 @@ __global__ __launch_bounds__(256) void k_pack_planes(const uint8_t *__restrict__
     }
 }
 
+// The steps of a store's creation (store_create_impl below).  PackJob: what the packing launches of one creation read.  Scratch (ASCII, offsets, first bad position) comes from the process-wide pool.
+struct PackJob {
+    DevBuf d_ascii{&g_scratch, SLOT_PACK_ASCII}, d_off{&g_scratch, SLOT_PACK_OFF}, d_bad{&g_scratch, SLOT_PACK_BAD};
+    uint64_t base = 0, total = 0;          // first byte of the set in the caller's offsets, bytes of the set
+    uint32_t n = 0, nchunks = 0;
+    uint64_t pack_waves = kPackWaves;
+};
+constexpr unsigned long long kNoBad = ~0ull;
+
+// every way out of a failed creation: the message, and the HIP error does not stay behind for the next call's check
+int create_failed(const char *message)
+{
+    g_last_error = message;
+    (void)hipGetLastError();
+    return ISOCON_E_HIP;
+}
+
+// issue(grid, w0) for the job's nchunks * n wavefronts (four to a block), pack_waves of them a launch
+template <class Issue>
+void for_wave_slices(const PackJob &job, Issue issue)
+{
+    const uint64_t waves = (uint64_t)job.nchunks * job.n;
+    for (uint64_t w0 = 0; w0 < waves; w0 += job.pack_waves) issue(dim3((unsigned)((std::min<uint64_t>(job.pack_waves, waves - w0) + 3) / 4)), w0);
+}
+
+// packs under `map`; fold == 0: *bad = the first position that holds a symbol outside it (kNoBad: none); fold == 1 reports nothing, bad == nullptr
+bool pack_planes(PackJob &job, uint64_t *planes, PackMap map, uint32_t fold, unsigned long long *bad)
+{
+    if (bad && hipMemcpy(job.d_bad.p, &kNoBad, 8, hipMemcpyHostToDevice) != hipSuccess) return false;
+    for_wave_slices(job, [&](dim3 grid, uint64_t w0) {
+        hipLaunchKernelGGL(k_pack_planes, grid, dim3(256), 0, 0, job.d_ascii.as<uint8_t>(), job.d_off.as<uint64_t>(), job.base, job.n, job.nchunks, planes,
+                           job.d_bad.as<unsigned long long>(), map, fold, w0);
+    });
+    return hipGetLastError() == hipSuccess && (!bad || hipMemcpy(bad, job.d_bad.p, 8, hipMemcpyDeviceToHost) == hipSuccess);
+}
+
+// The sequences at seq_ptrs[i] (offsets: the prefix sums of their lengths) -> d_dst as their concatenation, gathered into the two halves of the
+// pinned staging buffer: one half on its way to the device while the other is being filled.
+bool upload_gathered(char *d_dst, const uint8_t *const *seq_ptrs, const uint64_t *offsets, uint32_t n, uint64_t total)
+{
+    char *stg = static_cast<char *>(g_stage.get(kStageBytes));
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool up = stg != nullptr && hipEventCreateWithFlags(&ev[0], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&ev[1], hipEventDisableTiming) == hipSuccess;
+    const size_t half = kStageBytes / 2;
+    uint64_t done = 0;           // bytes of the concatenation already sent
+    bool busy[2] = {false, false};
+    const unsigned hc = std::thread::hardware_concurrency();
+    const unsigned n_thr = total >= ((uint64_t)8 << 20) ? std::min(4u, hc ? hc : 1u) : 1u;      // one thread copies ~10 GB/s: 125 MB at C3
+    for (int h = 0; up && done < total; h ^= 1) {
+        if (busy[h]) up = hipEventSynchronize(ev[h]) == hipSuccess;
+        const size_t fill = (size_t)std::min<uint64_t>(half, total - done);
+        if (n_thr <= 1) gather_bytes(stg + h * half, seq_ptrs, offsets, n, done, done + fill);
+        else {
+            std::thread th[4];
+            const size_t part = (fill + n_thr - 1) / n_thr;
+            for (unsigned t = 0; t < n_thr; ++t) {
+                const size_t a = std::min(fill, t * part), b = std::min(fill, (t + 1) * part);
+                th[t] = std::thread([=] { if (b > a) gather_bytes(stg + h * half + a, seq_ptrs, offsets, n, done + a, done + b); });
+            }
+            for (unsigned t = 0; t < n_thr; ++t) th[t].join();
+        }
+        up = up && hipMemcpyAsync(d_dst + done, stg + h * half, fill, hipMemcpyHostToDevice, 0) == hipSuccess && hipEventRecord(ev[h], 0) == hipSuccess;
+        busy[h] = true;
+        done += fill;
+    }
+    up = up && hipStreamSynchronize(0) == hipSuccess;
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    return up;
+}
+
+// how often every byte value occurs in the set
+bool byte_histogram(PackJob &job, unsigned long long (&hist)[256])
+{
+    DevBuf d_hist(&g_scratch, SLOT_PACK_HIST);
+    if (d_hist.alloc(256 * 8) != ISOCON_OK || hipMemset(d_hist.p, 0, 256 * 8) != hipSuccess) return false;
+    hipLaunchKernelGGL(k_byte_histogram, dim3(1024), dim3(256), 0, 0, job.d_ascii.as<uint8_t>(), job.total, d_hist.as<unsigned long long>());
+    return hipGetLastError() == hipSuccess && hipMemcpy(hist, d_hist.p, sizeof(hist), hipMemcpyDeviceToHost) == hipSuccess;
+}
+
+// More than four symbols: keep the bytes.
+// Planes: the "ACGT" map with lower case folded onto upper case and code 0 at every other byte.  For the pairs of ordinary
+// sequences they are what they always are; for a sequence with other bytes they hold its image under a map that MERGES symbol
+// classes, and merging classes can only turn mismatches into matches: d(image x, image y) <= d(x, y), so every lower bound
+// computed on the planes (q-gram bounds) holds for the sequences themselves.
+// The bytes and their offsets move from the scratch pool into the store, with one count per sequence.
+bool keep_bytes(isocon_store &st, PackJob &job)
+{
+    const uint32_t n = job.n, nn = std::max<uint32_t>(n, 1);
+    DevBuf d_flags(&g_scratch, SLOT_PACK_FLAGS);
+    st.exc.assign(nn, 0);
+    st.exc_count.assign(nn, 0);
+    if (d_flags.alloc((size_t)nn * 4) != ISOCON_OK || hipMemset(d_flags.p, 0, (size_t)nn * 4) != hipSuccess ||
+        hipMalloc((void **)&st.d_bytes, job.total ? job.total : 16) != hipSuccess || hipMalloc((void **)&st.d_boff, (size_t)(nn + 1) * 8) != hipSuccess)
+        return false;
+    if (!pack_planes(job, st.d_planes, PackMap{{'A', 'C', 'G', 'T'}}, 1u, nullptr)) return false;
+    for_wave_slices(job, [&](dim3 grid, uint64_t w0) {
+        hipLaunchKernelGGL(k_exception_flags, grid, dim3(256), 0, 0, job.d_ascii.as<uint8_t>(), job.d_off.as<uint64_t>(), job.base, n, job.nchunks, d_flags.as<uint32_t>(),
+                           (uint32_t)'A' | ((uint32_t)'C' << 8) | ((uint32_t)'G' << 16) | ((uint32_t)'T' << 24), w0);
+    });
+    if (hipGetLastError() != hipSuccess || hipMemcpy(st.exc_count.data(), d_flags.p, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(st.d_bytes, job.d_ascii.p, job.total, hipMemcpyDeviceToDevice) != hipSuccess ||
+        hipMemcpy(st.d_boff, job.d_off.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToDevice) != hipSuccess)
+        return false;
+    st.bytes_base = job.base;
+    for (uint32_t i = 0; i < n; ++i) { st.exc[i] = st.exc_count[i] != 0; st.n_exc += st.exc[i]; }
+    st.acgt = false;
+    st.device_bytes += job.total + (size_t)(nn + 1) * 8;
+    return true;
+}
+
+// At most four symbols, not all of them ACGT: the set is packed again under its own map -- A, C, G, T keep their codes if present, the other
+// symbols take the free codes in byte order -- and serves the distance / NN entry points.
+bool pack_own_alphabet(isocon_store &st, PackJob &job, const unsigned long long (&hist)[256])
+{
+    PackMap map{{0, 0, 0, 0}};
+    bool used[4] = {false, false, false, false};
+    const char acgt_sym[4] = {'A', 'C', 'G', 'T'};
+    for (int k = 0; k < 4; ++k) if (hist[(uint8_t)acgt_sym[k]]) { map.sym[k] = (uint8_t)acgt_sym[k]; used[k] = true; }
+    for (int c = 0; c < 256; ++c) {
+        if (!hist[c] || c == 'A' || c == 'C' || c == 'G' || c == 'T') continue;
+        for (int k = 0; k < 4; ++k) if (!used[k]) { map.sym[k] = (uint8_t)c; used[k] = true; break; }
+    }
+    // (free codes keep byte 0, which no sequence holds: C strings)  -- a 0 byte in the input would be one of the four symbols
+    for (int k = 0; k < 4; ++k) if (!used[k]) { for (int c = 1; c < 256; ++c) if (!hist[c] && c != map.sym[0] && c != map.sym[1] && c != map.sym[2] && c != map.sym[3]) { map.sym[k] = (uint8_t)c; break; } }
+    unsigned long long bad;
+    if (!pack_planes(job, st.d_planes, map, 0u, &bad) || bad != kNoBad) return false;
+    for (int k = 0; k < 4; ++k) st.alphabet[k] = (char)map.sym[k];
+    st.acgt = false;
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -524,180 +663,43 @@ static int store_create_impl(const uint8_t *ascii, const uint8_t *const *seq_ptr
 {
     *out = nullptr;
     int32_t maxlen = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 0x3fffffff) return ISOCON_E_ARG;
-        maxlen = std::max<int32_t>(maxlen, (int32_t)(offsets[i + 1] - offsets[i]));
-    }
-    const uint32_t nchunks = (uint32_t)((maxlen + 63) / 64 + 1);
     const uint32_t nn = std::max<uint32_t>(n, 1);
     std::vector<int32_t> lens(nn, 0);
-    for (uint32_t i = 0; i < n; ++i) lens[i] = (int32_t)(offsets[i + 1] - offsets[i]);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 0x3fffffff) return ISOCON_E_ARG;
+        lens[i] = (int32_t)(offsets[i + 1] - offsets[i]);
+        maxlen = std::max(maxlen, lens[i]);
+    }
+    const uint32_t nchunks = (uint32_t)((maxlen + 63) / 64 + 1);
     const uint64_t base = n ? offsets[0] : 0, total = n ? offsets[n] - offsets[0] : 0;
-    isocon_store *st = new isocon_store(private_scratch);
+    // the store is destroyed on every way out but the last line
+    std::unique_ptr<isocon_store, decltype(&isocon_store_destroy)> st(new isocon_store(private_scratch), isocon_store_destroy);
     st->lens = lens;
     st->maxlen = maxlen;
     const size_t pbytes = (size_t)nchunks * nn * 2 * sizeof(uint64_t), lbytes = lens.size() * sizeof(int32_t);
-    if (hipMalloc((void **)&st->d_planes, pbytes) != hipSuccess || hipMalloc((void **)&st->d_lens, lbytes) != hipSuccess) {
-        g_last_error = "hipMalloc(store) failed";
-        isocon_store_destroy(st);
-        return ISOCON_E_HIP;
-    }
+    if (hipMalloc((void **)&st->d_planes, pbytes) != hipSuccess || hipMalloc((void **)&st->d_lens, lbytes) != hipSuccess) return create_failed("hipMalloc(store) failed");
     // The bytes go to the device as they are and are packed there (k_pack_planes: one wavefront per 64 bases, two ballots);
-    // the host only checked the offsets.  Scratch (ASCII, offsets, first bad position) comes from the process-wide pool.
-    {
-        DevBuf d_ascii(&g_scratch, SLOT_PACK_ASCII), d_off(&g_scratch, SLOT_PACK_OFF), d_bad(&g_scratch, SLOT_PACK_BAD);
-        uint64_t pack_waves = kPackWaves;
-        if (const char *e = variant_value("pack_waves")) pack_waves = std::max<uint64_t>(4, strtoull(e, nullptr, 10)) & ~(uint64_t)3;      // tests: many launches on a small set
-        const unsigned long long none = ~0ull;
-        int rc = ISOCON_OK;
-        if ((rc = d_ascii.alloc(total ? total : 16)) || (rc = d_off.alloc((size_t)(nn + 1) * 8)) || (rc = d_bad.alloc(8))) { isocon_store_destroy(st); return rc; }
-        bool up = true;
-        if (total && ascii) up = copy_h2d(d_ascii.p, ascii + base, total) == hipSuccess;
-        else if (total) {
-            char *stg = static_cast<char *>(g_stage.get(kStageBytes));
-            hipEvent_t ev[2] = {nullptr, nullptr};
-            up = stg != nullptr && hipEventCreateWithFlags(&ev[0], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&ev[1], hipEventDisableTiming) == hipSuccess;
-            const size_t half = kStageBytes / 2;
-            uint64_t done = 0;           // bytes of the concatenation already sent
-            bool busy[2] = {false, false};
-            // bytes [b0, b1) of the concatenation -> dst (offsets[] are the sequences' prefix sums, relative to `base`)
-            auto gather = [&](char *dst, uint64_t b0, uint64_t b1) {
-                uint32_t i = (uint32_t)(std::upper_bound(offsets, offsets + n + 1, base + b0) - offsets) - 1;
-                uint64_t in_seq = base + b0 - offsets[i];
-                while (b0 < b1 && i < n) {
-                    const uint64_t len = offsets[i + 1] - offsets[i];
-                    const size_t take = (size_t)std::min<uint64_t>(len - in_seq, b1 - b0);
-                    if (take) memcpy(dst, seq_ptrs[i] + in_seq, take);
-                    dst += take; b0 += take; in_seq += take;
-                    if (in_seq == len) { ++i; in_seq = 0; }
-                }
-            };
-            const unsigned hc = std::thread::hardware_concurrency();
-            const unsigned n_thr = total >= ((uint64_t)8 << 20) ? std::min(4u, hc ? hc : 1u) : 1u;      // one thread copies ~10 GB/s: 125 MB at C3
-            for (int h = 0; up && done < total; h ^= 1) {
-                if (busy[h]) up = hipEventSynchronize(ev[h]) == hipSuccess;
-                const size_t fill = (size_t)std::min<uint64_t>(half, total - done);
-                if (n_thr <= 1) gather(stg + h * half, done, done + fill);
-                else {
-                    std::thread th[4];
-                    const size_t part = (fill + n_thr - 1) / n_thr;
-                    for (unsigned t = 0; t < n_thr; ++t) {
-                        const size_t a = std::min(fill, t * part), b = std::min(fill, (t + 1) * part);
-                        th[t] = std::thread([&, a, b, h] { if (b > a) gather(stg + h * half + a, done + a, done + b); });
-                    }
-                    for (unsigned t = 0; t < n_thr; ++t) th[t].join();
-                }
-                up = up && hipMemcpyAsync(static_cast<char *>(d_ascii.p) + done, stg + h * half, fill, hipMemcpyHostToDevice, 0) == hipSuccess &&
-                     hipEventRecord(ev[h], 0) == hipSuccess;
-                busy[h] = true;
-                done += fill;
-            }
-            up = up && hipStreamSynchronize(0) == hipSuccess;
-            if (ev[0]) (void)hipEventDestroy(ev[0]);
-            if (ev[1]) (void)hipEventDestroy(ev[1]);
-        }
-        bool ok = up &&
-                  (n == 0 || copy_h2d(d_off.p, offsets, (size_t)(n + 1) * 8) == hipSuccess) &&
-                  hipMemcpy(d_bad.p, &none, 8, hipMemcpyHostToDevice) == hipSuccess && copy_h2d(st->d_lens, lens.data(), lbytes) == hipSuccess;
-        unsigned long long bad = none;
-        if (ok) {
-            if (n) {
-                const uint64_t waves = (uint64_t)nchunks * n;
-                for (uint64_t w0 = 0; w0 < waves; w0 += pack_waves)
-                    hipLaunchKernelGGL(k_pack_planes, dim3((unsigned)((std::min<uint64_t>(pack_waves, waves - w0) + 3) / 4)), dim3(256), 0, 0, d_ascii.as<uint8_t>(), d_off.as<uint64_t>(), base, n, nchunks,
-                                       st->d_planes, d_bad.as<unsigned long long>(), PackMap{{'A', 'C', 'G', 'T'}}, 0u, w0);
-            } else {
-                ok = hipMemset(st->d_planes, 0, pbytes) == hipSuccess;
-            }
-            ok = ok && hipGetLastError() == hipSuccess && hipMemcpy(&bad, d_bad.p, 8, hipMemcpyDeviceToHost) == hipSuccess;
-        }
-        if (!ok) {
-            g_last_error = "isocon_store_create: device copy / packing failed";
-            (void)hipGetLastError();
-            isocon_store_destroy(st);
-            return ISOCON_E_HIP;
-        }
-        if (bad != none) {
-            // A symbol outside ACGT.  edlib takes any characters (EAM:111, NNG:105): if the whole set uses at most four distinct symbols
-            // (lower case, RNA ...) it is packed again under its own map -- A, C, G, T keep their codes if present, the other symbols take
-            // the free codes in byte order -- and serves the distance / NN entry points; more than four symbols cannot be held in 2 bits.
-            DevBuf d_hist(&g_scratch, SLOT_PACK_HIST);
-            unsigned long long hist[256];
-            bool hok = d_hist.alloc(256 * 8) == ISOCON_OK && hipMemset(d_hist.p, 0, 256 * 8) == hipSuccess;
-            if (hok) {
-                hipLaunchKernelGGL(k_byte_histogram, dim3(1024), dim3(256), 0, 0, d_ascii.as<uint8_t>(), (uint64_t)total, d_hist.as<unsigned long long>());
-                hok = hipGetLastError() == hipSuccess && hipMemcpy(hist, d_hist.p, sizeof(hist), hipMemcpyDeviceToHost) == hipSuccess;
-            }
-            int distinct = 0;
-            for (int c = 0; hok && c < 256; ++c) distinct += hist[c] != 0;
-            if (!hok) {
-                g_last_error = "isocon_store_create: symbol histogram failed";
-                (void)hipGetLastError();
-                isocon_store_destroy(st);
-                return ISOCON_E_HIP;
-            }
-            if (distinct > 4) {
-                // Planes: the "ACGT" map with lower case folded onto upper case and code 0 at every other byte.  For the pairs of ordinary
-                // sequences they are what they always are; for a sequence with other bytes they hold its image under a map that MERGES symbol
-                // classes, and merging classes can only turn mismatches into matches: d(image x, image y) <= d(x, y), so every lower bound
-                // computed on the planes (q-gram bounds) holds for the sequences themselves.
-                // The bytes and their offsets move from the scratch pool into the store, with one count per sequence.
-                DevBuf d_flags(&g_scratch, SLOT_PACK_FLAGS);
-                st->exc.assign(nn, 0);
-                st->exc_count.assign(nn, 0);
-                bool eok = d_flags.alloc((size_t)nn * 4) == ISOCON_OK && hipMemset(d_flags.p, 0, (size_t)nn * 4) == hipSuccess &&
-                           hipMalloc((void **)&st->d_bytes, total ? total : 16) == hipSuccess && hipMalloc((void **)&st->d_boff, (size_t)(nn + 1) * 8) == hipSuccess;
-                if (eok) {
-                    const uint64_t waves = (uint64_t)nchunks * n;
-                    for (uint64_t w0 = 0; w0 < waves; w0 += pack_waves)
-                    hipLaunchKernelGGL(k_pack_planes, dim3((unsigned)((std::min<uint64_t>(pack_waves, waves - w0) + 3) / 4)), dim3(256), 0, 0, d_ascii.as<uint8_t>(), d_off.as<uint64_t>(), base, n, nchunks,
-                                       st->d_planes, d_bad.as<unsigned long long>(), PackMap{{'A', 'C', 'G', 'T'}}, 1u, w0);
-                    for (uint64_t w0 = 0; w0 < waves; w0 += pack_waves)
-                        hipLaunchKernelGGL(k_exception_flags, dim3((unsigned)((std::min<uint64_t>(pack_waves, waves - w0) + 3) / 4)), dim3(256), 0, 0, d_ascii.as<uint8_t>(), d_off.as<uint64_t>(), base, n,
-                                           nchunks, d_flags.as<uint32_t>(), (uint32_t)'A' | ((uint32_t)'C' << 8) | ((uint32_t)'G' << 16) | ((uint32_t)'T' << 24), w0);
-                    eok = hipGetLastError() == hipSuccess && hipMemcpy(st->exc_count.data(), d_flags.p, (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-                          hipMemcpy(st->d_bytes, d_ascii.p, total, hipMemcpyDeviceToDevice) == hipSuccess &&
-                          hipMemcpy(st->d_boff, d_off.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToDevice) == hipSuccess;
-                }
-                if (!eok) {
-                    g_last_error = "isocon_store_create: keeping the bytes of a set with more than four symbols failed";
-                    (void)hipGetLastError();
-                    isocon_store_destroy(st);
-                    return ISOCON_E_HIP;
-                }
-                st->bytes_base = base;
-                for (uint32_t i = 0; i < n; ++i) { st->exc[i] = st->exc_count[i] != 0; st->n_exc += st->exc[i]; }
-                st->acgt = false;
-                st->device_bytes += total + (size_t)(nn + 1) * 8;
-            } else {
-            PackMap map{{0, 0, 0, 0}};
-            bool used[4] = {false, false, false, false};
-            const char acgt_sym[4] = {'A', 'C', 'G', 'T'};
-            for (int k = 0; k < 4; ++k) if (hist[(uint8_t)acgt_sym[k]]) { map.sym[k] = (uint8_t)acgt_sym[k]; used[k] = true; }
-            for (int c = 0; c < 256; ++c) {
-                if (!hist[c] || c == 'A' || c == 'C' || c == 'G' || c == 'T') continue;
-                for (int k = 0; k < 4; ++k) if (!used[k]) { map.sym[k] = (uint8_t)c; used[k] = true; break; }
-            }
-            // (free codes keep byte 0, which no sequence holds: C strings)  -- a 0 byte in the input would be one of the four symbols
-            for (int k = 0; k < 4; ++k) if (!used[k]) { for (int c = 1; c < 256; ++c) if (!hist[c] && c != map.sym[0] && c != map.sym[1] && c != map.sym[2] && c != map.sym[3]) { map.sym[k] = (uint8_t)c; break; } }
-            bool rok = hipMemcpy(d_bad.p, &none, 8, hipMemcpyHostToDevice) == hipSuccess;
-            if (rok) {
-                const uint64_t waves = (uint64_t)nchunks * n;
-                for (uint64_t w0 = 0; w0 < waves; w0 += pack_waves)
-                    hipLaunchKernelGGL(k_pack_planes, dim3((unsigned)((std::min<uint64_t>(pack_waves, waves - w0) + 3) / 4)), dim3(256), 0, 0, d_ascii.as<uint8_t>(), d_off.as<uint64_t>(), base, n, nchunks,
-                                       st->d_planes, d_bad.as<unsigned long long>(), map, 0u, w0);
-                rok = hipGetLastError() == hipSuccess && hipMemcpy(&bad, d_bad.p, 8, hipMemcpyDeviceToHost) == hipSuccess && bad == none;
-            }
-            if (!rok) {
-                g_last_error = "isocon_store_create: packing under the set's own alphabet failed";
-                (void)hipGetLastError();
-                isocon_store_destroy(st);
-                return ISOCON_E_HIP;
-            }
-            for (int k = 0; k < 4; ++k) st->alphabet[k] = (char)map.sym[k];
-            st->acgt = false;
-            }
-        }
+    // the host only checked the offsets.
+    PackJob job;
+    job.base = base; job.total = total; job.n = n; job.nchunks = nchunks;
+    if (const char *e = variant_value("pack_waves")) job.pack_waves = std::max<uint64_t>(4, strtoull(e, nullptr, 10)) & ~(uint64_t)3;      // tests: many launches on a small set
+    int rc;
+    if ((rc = job.d_ascii.alloc(total ? total : 16)) || (rc = job.d_off.alloc((size_t)(nn + 1) * 8)) || (rc = job.d_bad.alloc(8))) return rc;
+    bool ok = !total || (ascii ? copy_h2d(job.d_ascii.p, ascii + base, total) == hipSuccess : upload_gathered(job.d_ascii.as<char>(), seq_ptrs, offsets, n, total));
+    ok = ok && (n == 0 || copy_h2d(job.d_off.p, offsets, (size_t)(n + 1) * 8) == hipSuccess) && copy_h2d(st->d_lens, lens.data(), lbytes) == hipSuccess;
+    unsigned long long bad = kNoBad;
+    if (ok) ok = n ? pack_planes(job, st->d_planes, PackMap{{'A', 'C', 'G', 'T'}}, 0u, &bad) : hipMemset(st->d_planes, 0, pbytes) == hipSuccess;
+    if (!ok) return create_failed("isocon_store_create: device copy / packing failed");
+    if (bad != kNoBad) {
+        // A symbol outside ACGT.  edlib takes any characters (EAM:111, NNG:105): if the whole set uses at most four distinct symbols
+        // (lower case, RNA ...) it is packed again under its own map; more than four symbols cannot be held in 2 bits.
+        unsigned long long hist[256];
+        if (!byte_histogram(job, hist)) return create_failed("isocon_store_create: symbol histogram failed");
+        int distinct = 0;
+        for (int c = 0; c < 256; ++c) distinct += hist[c] != 0;
+        if (distinct > 4) {
+            if (!keep_bytes(*st, job)) return create_failed("isocon_store_create: keeping the bytes of a set with more than four symbols failed");
+        } else if (!pack_own_alphabet(*st, job, hist)) return create_failed("isocon_store_create: packing under the set's own alphabet failed");
     }
     st->device_bytes += pbytes + lbytes;
     st->dev.planes = st->d_planes;
@@ -706,7 +708,7 @@ static int store_create_impl(const uint8_t *ascii, const uint8_t *const *seq_ptr
     st->dev.n = n;
     st->dev.nchunks = nchunks;
     st->lens.resize(n);
-    *out = st;
+    *out = st.release();
     return ISOCON_OK;
 }
 
@@ -718,13 +720,7 @@ int isocon_store_create(const uint8_t *ascii, const uint64_t *offsets, uint32_t 
 
 int isocon_store_create_ptrs(const uint8_t *const *seq_ptrs, const uint64_t *seq_lens, uint32_t n, isocon_store **out)
 {
-    if (!out || (n && (!seq_ptrs || !seq_lens))) return ISOCON_E_ARG;
-    std::vector<uint64_t> offsets((size_t)n + 1, 0);
-    for (uint32_t i = 0; i < n; ++i) {
-        if (seq_lens[i] && !seq_ptrs[i]) return ISOCON_E_ARG;
-        offsets[i + 1] = offsets[i] + seq_lens[i];
-    }
-    return store_create_impl(nullptr, seq_ptrs, offsets.data(), n, out);
+    return isocon_store_create_ptrs_ex(seq_ptrs, seq_lens, n, 0u, out);
 }
 
 int isocon_store_create_ptrs_ex(const uint8_t *const *seq_ptrs, const uint64_t *seq_lens, uint32_t n, uint32_t flags, isocon_store **out)
@@ -776,124 +772,102 @@ uint64_t isocon_store_device_bytes(const isocon_store *s) { return s ? s->device
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 
-template <int W>
-int launch_band_tiles(isocon_store *st, const DevStore &S, const std::vector<uint32_t> &tile_shared, const std::vector<uint32_t> &lane_ids,
-                      const std::vector<int32_t> &lane_k, std::vector<int32_t> &out, EventTimer &tm)
-{
-    const size_t nt = tile_shared.size();
-    out.assign(nt * 64, -1);
-    if (!nt) return ISOCON_OK;
-    DevBuf d_ts(&st->pool, SLOT_ED_TS), d_ids(&st->pool, SLOT_ED_IDS), d_k(&st->pool, SLOT_ED_K), d_out(&st->pool, SLOT_ED_OUT);
-    int rc;
-    if ((rc = d_ts.alloc(nt * 4)) || (rc = d_ids.alloc(nt * 64 * 4)) || (rc = d_k.alloc(nt * 64 * 4)) || (rc = d_out.alloc(nt * 64 * 4))) return rc;
-    ISO_HIP_CHECK(copy_h2d(d_ts.p, tile_shared.data(), nt * 4));
-    ISO_HIP_CHECK(copy_h2d(d_ids.p, lane_ids.data(), nt * 64 * 4));
-    ISO_HIP_CHECK(copy_h2d(d_k.p, lane_k.data(), nt * 64 * 4));
-    tm.start();
-    hipLaunchKernelGGL(k_ed_band_tiles<W>, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, 0, S, d_ts.as<uint32_t>(),
-                       d_ids.as<uint32_t>(), d_k.as<int32_t>(), d_out.as<int32_t>(), (uint32_t)nt);
-    ISO_HIP_CHECK(hipGetLastError());
-    tm.stop();
-    ISO_HIP_CHECK(copy_d2h(out.data(), d_out.p, nt * 64 * 4));
-    return ISOCON_OK;
-}
-
-int run_band_stage(int W, isocon_store *st, const DevStore &S, const std::vector<uint32_t> &ts, const std::vector<uint32_t> &ids,
-                   const std::vector<int32_t> &ks, std::vector<int32_t> &out, EventTimer &tm)
-{
-    switch (W) {
-    case 1: return launch_band_tiles<1>(st, S, ts, ids, ks, out, tm);
-    case 2: return launch_band_tiles<2>(st, S, ts, ids, ks, out, tm);
-    case 4: return launch_band_tiles<4>(st, S, ts, ids, ks, out, tm);
-    case 8: return launch_band_tiles<8>(st, S, ts, ids, ks, out, tm);
-    default: return ISOCON_E_ARG;
+// The stages of a pair list on the device: the three of ed_pairs_plan.hpp and the byte-wise one in front of them.
+struct DeviceStages {
+    using Ids = std::vector<uint32_t>;
+    using Ints = std::vector<int32_t>;
+    isocon_store *st;
+    EventTimer &tm;
+    // One stage: its three input arrays go up into the scratch slots slot0 .. slot0 + 2, `launch(in0, in1, in2, out)` issues the kernel between
+    // the timer's events (kernel_ms: the launches, copies excluded), n_out answers come down through slot0 + 3.
+    template <class Launch>
+    int run(int slot0, const Ids &in0, const Ids &in1, const Ints &in2, size_t n_out, Ints &out, Launch launch)
+    {
+        static_assert(SLOT_ED_OUT == SLOT_ED_TS + 3 && SLOT_FULL_OUT == SLOT_FULL_A + 3 && SLOT_EB_OUT == SLOT_EB_A + 3, "a stage's four slots are consecutive");
+        out.assign(n_out, -1);
+        if (!n_out) return ISOCON_OK;
+        DevBuf d0(&st->pool, slot0), d1(&st->pool, slot0 + 1), d2(&st->pool, slot0 + 2), d_out(&st->pool, slot0 + 3);
+        int rc;
+        if ((rc = d0.upload(in0.data(), in0.size() * 4)) || (rc = d1.upload(in1.data(), in1.size() * 4)) || (rc = d2.upload(in2.data(), in2.size() * 4)) || (rc = d_out.alloc(n_out * 4)))
+            return rc;
+        tm.start();
+        launch(d0.as<uint32_t>(), d1.as<uint32_t>(), d2.as<int32_t>(), d_out.as<int32_t>());
+        ISO_HIP_CHECK(hipGetLastError());
+        tm.stop();
+        ISO_HIP_CHECK(copy_d2h(out.data(), d_out.p, n_out * 4));
+        return ISOCON_OK;
     }
-}
-
-int run_full(isocon_store *st, const std::vector<uint32_t> &a, const std::vector<uint32_t> &b,
-             const std::vector<int32_t> &k, std::vector<int32_t> &out, EventTimer &tm)
-{
-    const size_t np = a.size();
-    out.assign(np, -1);
-    if (!np) return ISOCON_OK;
-    DevBuf d_a(&st->pool, SLOT_FULL_A), d_b(&st->pool, SLOT_FULL_B), d_k(&st->pool, SLOT_FULL_K), d_out(&st->pool, SLOT_FULL_OUT);
-    int rc;
-    if ((rc = d_a.alloc(np * 4)) || (rc = d_b.alloc(np * 4)) || (rc = d_k.alloc(np * 4)) || (rc = d_out.alloc(np * 4))) return rc;
-    ISO_HIP_CHECK(copy_h2d(d_a.p, a.data(), np * 4));
-    ISO_HIP_CHECK(copy_h2d(d_b.p, b.data(), np * 4));
-    ISO_HIP_CHECK(copy_h2d(d_k.p, k.data(), np * 4));
-    bool multipass = false;
-    int32_t maxtext = 0;
-    for (size_t p = 0; p < np; ++p) {
-        const int32_t la = st->lens[a[p]], lb = st->lens[b[p]];
-        if (std::min(la, lb) > 4096) multipass = true;
-        maxtext = std::max(maxtext, std::max(la, lb));
+    // (shares the tiles' slots: the two never hold data at the same time)
+    int lanes(const Ids &a, const Ids &b, const Ints &k, Ints &out)
+    {
+        const size_t np = a.size();
+        NNParams none;
+        memset(&none, 0, sizeof(none));
+        return run(SLOT_ED_TS, a, b, k, np, out, [&](uint32_t *da, uint32_t *db, int32_t *dk, int32_t *res) {
+            hipLaunchKernelGGL(k_ed_lanes<false>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, 0, st->dev, none, da, db, dk, (uint64_t)np, res);
+        });
     }
-    const size_t lds = multipass ? (size_t)((maxtext + 15) & ~15) : 0;
-    if (lds > 160 * 1024) { g_last_error = "sequence longer than 163840 bases in the un-banded kernel"; return ISOCON_E_UNSUPPORTED; }
-    if (lds > 64 * 1024)
-        ISO_HIP_CHECK(hipFuncSetAttribute((const void *)k_ed_full, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    tm.start();
-    hipLaunchKernelGGL(k_ed_full, dim3((unsigned)np), dim3(64), lds, 0, st->dev, d_a.as<uint32_t>(), d_b.as<uint32_t>(),
-                       d_k.as<int32_t>(), d_out.as<int32_t>(), (uint32_t)np);
-    ISO_HIP_CHECK(hipGetLastError());
-    tm.stop();
-    ISO_HIP_CHECK(copy_d2h(out.data(), d_out.p, np * 4));
-    return ISOCON_OK;
-}
-
-// k < 0: unbounded.  One wavefront per pair, a grid of at most 8192 that strides over the list (each needs a row buffer).
-int run_bytes(isocon_store *st, const std::vector<uint32_t> &a, const std::vector<uint32_t> &b, const std::vector<int32_t> &k, std::vector<int32_t> &out, EventTimer &tm)
-{
-    const size_t np = a.size();
-    out.assign(np, -1);
-    if (!np) return ISOCON_OK;
-    if (!st->d_bytes) { g_last_error = "internal: byte-wise distances on a store that kept no bytes"; return ISOCON_E_HIP; }
-    if (st->maxlen >= (int32_t)EB_INF - 1) { g_last_error = "byte-wise distances: sequences of 8 388 606 bases and more are not supported"; return ISOCON_E_UNSUPPORTED; }
-    const uint32_t row_stride = (uint32_t)st->maxlen + 130u;
-    size_t waves = std::min<size_t>(np, 8192);
-    while (waves > 256 && waves * row_stride * 4 > ((size_t)2 << 30)) waves /= 2;
-    DevBuf d_a(&st->pool, SLOT_EB_A), d_b(&st->pool, SLOT_EB_B), d_k(&st->pool, SLOT_EB_K), d_out(&st->pool, SLOT_EB_OUT), d_rows(&st->pool, SLOT_EB_ROWS);
-    int rc;
-    if ((rc = d_a.alloc(np * 4)) || (rc = d_b.alloc(np * 4)) || (rc = d_k.alloc(np * 4)) || (rc = d_out.alloc(np * 4)) || (rc = d_rows.alloc(waves * row_stride * 4))) return rc;
-    ISO_HIP_CHECK(copy_h2d(d_a.p, a.data(), np * 4));
-    ISO_HIP_CHECK(copy_h2d(d_b.p, b.data(), np * 4));
-    ISO_HIP_CHECK(copy_h2d(d_k.p, k.data(), np * 4));
-    tm.start();
-    hipLaunchKernelGGL(k_ed_bytes, dim3((unsigned)waves), dim3(64), 0, 0, ByteStore{st->d_bytes, st->d_boff, st->bytes_base, st->d_lens}, d_a.as<uint32_t>(), d_b.as<uint32_t>(),
-                       d_k.as<int32_t>(), (unsigned long long)np, d_rows.as<uint32_t>(), row_stride, d_out.as<int32_t>());
-    ISO_HIP_CHECK(hipGetLastError());
-    tm.stop();
-    ISO_HIP_CHECK(copy_d2h(out.data(), d_out.p, np * 4));
-    return ISOCON_OK;
-}
+    int tiles(int W, const Ids &tile_shared, const Ids &lane_ids, const Ints &lane_k, Ints &out)
+    {
+        const auto kernel = W == 1 ? k_ed_band_tiles<1> : W == 2 ? k_ed_band_tiles<2> : W == 4 ? k_ed_band_tiles<4> : W == 8 ? k_ed_band_tiles<8> : nullptr;
+        if (!kernel) return ISOCON_E_ARG;
+        const size_t nt = tile_shared.size();
+        return run(SLOT_ED_TS, tile_shared, lane_ids, lane_k, nt * 64, out, [&](uint32_t *ts, uint32_t *ids, int32_t *ks, int32_t *res) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, 0, st->dev, ts, ids, ks, res, (uint32_t)nt);
+        });
+    }
+    int full(const Ids &a, const Ids &b, const Ints &k, Ints &out)
+    {
+        const size_t np = a.size();
+        bool multipass = false;
+        int32_t maxtext = 0;
+        for (size_t p = 0; p < np; ++p) {
+            const int32_t la = st->lens[a[p]], lb = st->lens[b[p]];
+            if (std::min(la, lb) > 4096) multipass = true;
+            maxtext = std::max(maxtext, std::max(la, lb));
+        }
+        const size_t lds = multipass ? (size_t)((maxtext + 15) & ~15) : 0;
+        if (lds > 160 * 1024) { g_last_error = "sequence longer than 163840 bases in the un-banded kernel"; return ISOCON_E_UNSUPPORTED; }
+        if (lds > 64 * 1024)
+            ISO_HIP_CHECK(hipFuncSetAttribute((const void *)k_ed_full, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        return run(SLOT_FULL_A, a, b, k, np, out, [&](uint32_t *da, uint32_t *db, int32_t *dk, int32_t *res) {
+            hipLaunchKernelGGL(k_ed_full, dim3((unsigned)np), dim3(64), lds, 0, st->dev, da, db, dk, res, (uint32_t)np);
+        });
+    }
+    // k < 0: unbounded.  One wavefront per pair, a grid of at most 8192 that strides over the list (each needs a row buffer).
+    int bytes(const Ids &a, const Ids &b, const Ints &k, Ints &out)
+    {
+        const size_t np = a.size();          // (not 0: the caller has such pairs)
+        if (!st->d_bytes) { g_last_error = "internal: byte-wise distances on a store that kept no bytes"; return ISOCON_E_HIP; }
+        if (st->maxlen >= (int32_t)EB_INF - 1) { g_last_error = "byte-wise distances: sequences of 8 388 606 bases and more are not supported"; return ISOCON_E_UNSUPPORTED; }
+        const uint32_t row_stride = (uint32_t)st->maxlen + 130u;
+        size_t waves = std::min<size_t>(np, 8192);
+        while (waves > 256 && waves * row_stride * 4 > ((size_t)2 << 30)) waves /= 2;
+        DevBuf d_rows(&st->pool, SLOT_EB_ROWS);
+        if (int rc = d_rows.alloc(waves * row_stride * 4)) return rc;
+        return run(SLOT_EB_A, a, b, k, np, out, [&](uint32_t *da, uint32_t *db, int32_t *dk, int32_t *res) {
+            hipLaunchKernelGGL(k_ed_bytes, dim3((unsigned)waves), dim3(64), 0, 0, ByteStore{st->d_bytes, st->d_boff, st->bytes_base, st->d_lens}, da, db, dk,
+                               (unsigned long long)np, d_rows.as<uint32_t>(), row_stride, res);
+        });
+    }
+};
 
 }  // namespace
 
 namespace isocon {
 
 // Shared by isocon_ed_pairs and the NN fallback: exact bounded/unbounded distances for an explicit pair list.
-// Stages: 64-row band (k <= 63), 128, 256, 512 rows, then the un-banded kernel.
+// Stages: 64-row band (k <= 63), 128, 256, 512 rows, then the un-banded kernel; which pair goes where: ed_pairs_plan.hpp.
 // images: distances of the sequences' IMAGES in the planes (a set with more than four symbols: lower bounds of the true distances, see
 // isocon_store) -- the pairs of exceptional sequences are not split off to the byte-wise kernel.
 int ed_pairs_impl(isocon_store *st, const uint32_t *a, const uint32_t *b, const int32_t *k, uint64_t n_pairs,
                   int32_t *out_ed, float *kernel_ms, uint64_t *full_pairs, bool images)
 {
     EventTimer tm;
+    DeviceStages stages{st, tm};
     const uint32_t n = st->dev.n;
     for (uint64_t p = 0; p < n_pairs; ++p)
         if (a[p] >= n || b[p] >= n) return ISOCON_E_ARG;
-    // which side is shared more often?  (edit distance is symmetric)
-    bool swap_roles = false;
-    {
-        std::vector<uint8_t> seen_a(n, 0), seen_b(n, 0);
-        size_t da = 0, db = 0;
-        for (uint64_t p = 0; p < n_pairs; ++p) {
-            if (!seen_a[a[p]]) { seen_a[a[p]] = 1; ++da; }
-            if (!seen_b[b[p]]) { seen_b[b[p]] = 1; ++db; }
-        }
-        swap_roles = db < da;
-    }
     std::vector<uint64_t> pending;
     pending.reserve(n_pairs);
     if (st->n_exc && !images) {
@@ -904,130 +878,17 @@ int ed_pairs_impl(isocon_store *st, const uint32_t *a, const uint32_t *b, const 
             std::vector<uint32_t> xa(xp.size()), xb(xp.size());
             std::vector<int32_t> xk(xp.size()), res;
             for (size_t i = 0; i < xp.size(); ++i) { xa[i] = a[xp[i]]; xb[i] = b[xp[i]]; xk[i] = k ? k[xp[i]] : -1; }
-            int rc = run_bytes(st, xa, xb, xk, res, tm);
-            if (rc) return rc;
+            if (int rc = stages.bytes(xa, xb, xk, res)) return rc;
             for (size_t i = 0; i < xp.size(); ++i) out_ed[xp[i]] = res[i];
         }
     } else {
         pending.resize(n_pairs);
         std::iota(pending.begin(), pending.end(), 0);
     }
-    static const int stages[4] = {1, 2, 4, 8};
-    for (int si = 0; si < 4 && !pending.empty(); ++si) {
-        const int W = stages[si];
-        const int32_t kcap = 64 * W - 1;
-        auto sh = [&](uint64_t p) { return swap_roles ? b[p] : a[p]; };
-        auto ln = [&](uint64_t p) { return swap_roles ? a[p] : b[p]; };
-        std::sort(pending.begin(), pending.end(), [&](uint64_t x, uint64_t y) {
-            if (sh(x) != sh(y)) return sh(x) < sh(y);
-            const int32_t lx = st->lens[ln(x)], ly = st->lens[ln(y)];
-            if (lx != ly) return lx < ly;
-            return x < y;
-        });
-        std::vector<uint64_t> todo = pending, next;
-        if (W == 1) {
-            // Pairs that share their sequence with fewer than 16 others would leave most lanes of a tile empty: one pair per
-            // lane instead (ed_lanes.hpp; ~1.7x the column cost, every lane busy).  ISOCON_DEBUG_VARIANT=ed_lanes=1 / =0: all / none.
-            const char *e = variant_value("ed_lanes");
-            const size_t min_group = e ? (atoi(e) ? (size_t)-1 : 0) : 16;
-            std::vector<uint64_t> lanes_p, tiles_p;
-            for (size_t i = 0; i < todo.size();) {
-                size_t j = i;
-                while (j < todo.size() && sh(todo[j]) == sh(todo[i])) ++j;
-                std::vector<uint64_t> &dst = (j - i) < min_group ? lanes_p : tiles_p;
-                dst.insert(dst.end(), todo.begin() + i, todo.begin() + j);
-                i = j;
-            }
-            if (!lanes_p.empty()) {
-                const size_t np = lanes_p.size();
-                std::vector<uint32_t> la(np), lb2(np);
-                std::vector<int32_t> lk(np), res(np, -1);
-                for (size_t i = 0; i < np; ++i) {
-                    const uint64_t p = lanes_p[i];
-                    la[i] = a[p]; lb2[i] = b[p];
-                    const int32_t kr = k ? k[p] : -1;
-                    lk[i] = kr < 0 ? kcap : std::min(kr, kcap);
-                }
-                DevBuf d_a(&st->pool, SLOT_ED_TS), d_b(&st->pool, SLOT_ED_IDS), d_k(&st->pool, SLOT_ED_K), d_out(&st->pool, SLOT_ED_OUT);
-                int rc;
-                if ((rc = d_a.alloc(np * 4)) || (rc = d_b.alloc(np * 4)) || (rc = d_k.alloc(np * 4)) || (rc = d_out.alloc(np * 4))) return rc;
-                ISO_HIP_CHECK(copy_h2d(d_a.p, la.data(), np * 4));
-                ISO_HIP_CHECK(copy_h2d(d_b.p, lb2.data(), np * 4));
-                ISO_HIP_CHECK(copy_h2d(d_k.p, lk.data(), np * 4));
-                NNParams none;
-                memset(&none, 0, sizeof(none));
-                tm.start();
-                hipLaunchKernelGGL(k_ed_lanes<false>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, 0, st->dev, none, d_a.as<uint32_t>(), d_b.as<uint32_t>(),
-                                   d_k.as<int32_t>(), (uint64_t)np, d_out.as<int32_t>());
-                ISO_HIP_CHECK(hipGetLastError());
-                tm.stop();
-                ISO_HIP_CHECK(copy_d2h(res.data(), d_out.p, np * 4));
-                for (size_t i = 0; i < np; ++i) {
-                    const uint64_t p = lanes_p[i];
-                    const int32_t kr = k ? k[p] : -1;
-                    if (res[i] >= 0) out_ed[p] = res[i];
-                    else if (kr >= 0 && kr <= kcap) out_ed[p] = -1;
-                    else next.push_back(p);
-                }
-            }
-            todo.swap(tiles_p);
-        }
-        for (int round = 0; round < 2 && !todo.empty(); ++round) {
-            // round 0: tiles of up to 64 lanes per shared sequence; round 1: one lane per tile for pairs whose
-            // tile could not certify the threshold (heterogeneous length differences)
-            std::vector<uint32_t> ts, ids;
-            std::vector<int32_t> ks;
-            std::vector<uint64_t> slot_pair;
-            size_t i = 0;
-            while (i < todo.size()) {
-                size_t j = i;
-                const uint32_t s0 = sh(todo[i]);
-                const size_t lim = round == 0 ? 64 : 1;
-                while (j < todo.size() && j - i < lim && sh(todo[j]) == s0) ++j;
-                ts.push_back(s0);
-                for (size_t l = 0; l < 64; ++l) {
-                    if (i + l < j) {
-                        const uint64_t p = todo[i + l];
-                        ids.push_back(ln(p));
-                        const int32_t kr = k ? k[p] : -1;
-                        ks.push_back(kr < 0 ? kcap : std::min(kr, kcap));
-                        slot_pair.push_back(p);
-                    } else {
-                        ids.push_back(0xffffffffu);
-                        ks.push_back(-1);
-                        slot_pair.push_back(~(uint64_t)0);
-                    }
-                }
-                i = j;
-            }
-            std::vector<int32_t> res;
-            int rc = run_band_stage(W, st, st->dev, ts, ids, ks, res, tm);
-            if (rc) return rc;
-            std::vector<uint64_t> retry;
-            for (size_t sidx = 0; sidx < slot_pair.size(); ++sidx) {
-                const uint64_t p = slot_pair[sidx];
-                if (p == ~(uint64_t)0) continue;
-                const int32_t r = res[sidx];
-                const int32_t kr = k ? k[p] : -1;
-                if (r >= 0) out_ed[p] = r;
-                else if (r == -2) retry.push_back(p);
-                else if (kr >= 0 && kr <= kcap) out_ed[p] = -1;
-                else next.push_back(p);
-            }
-            todo.swap(retry);
-        }
-        if (!todo.empty()) { g_last_error = "internal: single-lane tile undetermined"; return ISOCON_E_HIP; }
-        pending.swap(next);
-    }
-    if (full_pairs) *full_pairs = pending.size();
-    if (!pending.empty()) {
-        std::vector<uint32_t> fa, fb;
-        std::vector<int32_t> fk, res;
-        for (uint64_t p : pending) { fa.push_back(a[p]); fb.push_back(b[p]); fk.push_back(k ? k[p] : -1); }
-        int rc = run_full(st, fa, fb, fk, res, tm);
-        if (rc) return rc;
-        for (size_t i = 0; i < pending.size(); ++i) out_ed[pending[i]] = res[i];
-    }
+    // ISOCON_DEBUG_VARIANT=ed_lanes=1 / =0: all / none of the pairs one per lane, whatever the size of their group
+    const char *e = variant_value("ed_lanes");
+    const size_t min_group = e ? (atoi(e) ? (size_t)-1 : 0) : 16;
+    if (int rc = ed_pairs_plan(st->lens.data(), n, a, b, k, n_pairs, std::move(pending), min_group, stages, out_ed, full_pairs, g_last_error)) return rc;
     if (kernel_ms) *kernel_ms = tm.total;
     return ISOCON_OK;
 }
@@ -1088,12 +949,10 @@ int qgram_bounds_for_pairs(isocon_store *s, const uint32_t *a, const uint32_t *b
     const uint32_t n_pad = std::max<uint32_t>(QM_TILE, ((n + QM_TILE - 1) / QM_TILE) * QM_TILE);
     DevBuf d_prof(&s->pool, SLOT_NN_QPROF), d_sum(&s->pool, SLOT_NN_QSUM), d_a(&s->pool, SLOT_ED_TS), d_b(&s->pool, SLOT_ED_IDS), d_out(&s->pool, SLOT_ED_OUT);
     int rc;
-    if ((rc = d_prof.alloc((size_t)n_pad * (QM_K / 2))) || (rc = d_sum.alloc((size_t)n * 4)) || (rc = d_a.alloc(n_pairs * 4)) || (rc = d_b.alloc(n_pairs * 4)) ||
-        (rc = d_out.alloc(n_pairs * 4)))
+    if ((rc = d_prof.alloc((size_t)n_pad * (QM_K / 2))) || (rc = d_sum.alloc((size_t)n * 4)) || (rc = d_a.upload(a, n_pairs * 4)) ||
+        (rc = d_b.upload(b, n_pairs * 4)) || (rc = d_out.alloc(n_pairs * 4)))
         return rc;
     s->pool.bound_tag.valid = false;          // the profile slot is shared with the bound matrix builds
-    ISO_HIP_CHECK(copy_h2d(d_a.p, a, n_pairs * 4));
-    ISO_HIP_CHECK(copy_h2d(d_b.p, b, n_pairs * 4));
     EventTimer tm;
     tm.start();
     hipLaunchKernelGGL(k_qgram_profile4, dim3((n + QP_SEQS - 1) / QP_SEQS), dim3(256), 0, 0, s->dev, d_prof.as<uint8_t>(), d_sum.as<uint32_t>(), n_pad,
@@ -1139,9 +998,8 @@ extern "C" int isocon_block_bound_pairs(isocon_store *s, const uint32_t *owner, 
     const uint32_t stride = nnf_text2_stride(s->maxlen);
     DevBuf d_text(&s->pool, SLOT_NN_TEXT2), d_a(&s->pool, SLOT_ED_TS), d_b(&s->pool, SLOT_ED_IDS), d_out(&s->pool, SLOT_ED_OUT);
     int rc;
-    if ((rc = d_text.alloc((size_t)n * stride * 4)) || (rc = d_a.alloc(n_pairs * 4)) || (rc = d_b.alloc(n_pairs * 4)) || (rc = d_out.alloc(n_pairs * 4))) return rc;
-    ISO_HIP_CHECK(copy_h2d(d_a.p, owner, n_pairs * 4));
-    ISO_HIP_CHECK(copy_h2d(d_b.p, partner, n_pairs * 4));
+    if ((rc = d_text.alloc((size_t)n * stride * 4)) || (rc = d_a.upload(owner, n_pairs * 4)) || (rc = d_b.upload(partner, n_pairs * 4)) || (rc = d_out.alloc(n_pairs * 4)))
+        return rc;
     hipLaunchKernelGGL(k_build_text2, dim3(n), dim3(256), 0, 0, s->dev, d_text.as<uint32_t>(), stride);
     hipLaunchKernelGGL(k_nn_block_count_pairs, dim3((unsigned)n_pairs), dim3(256), 0, 0, d_text.as<uint32_t>(), stride, s->dev.lens, d_a.as<uint32_t>(), d_b.as<uint32_t>(), d_out.as<int32_t>(), probe_stride);
     ISO_HIP_CHECK(hipGetLastError());
@@ -1195,14 +1053,11 @@ extern "C" int isocon_block_filter_chunks(isocon_store *s, const int32_t *thr, u
     DevBuf d_text(&s->pool, SLOT_NN_TEXT2), d_meta(&s->pool, SLOT_NN_LDEST), d_tot(&s->pool, SLOT_NN_LTOT), d_chunks(&s->pool, SLOT_NN_LCHUNKS), d_list(&s->pool, SLOT_NN_LIST),
         d_pa(&s->pool, SLOT_NN_LPA), d_pb(&s->pool, SLOT_NN_LPB), d_tasks(&s->pool, SLOT_NN_LTASKS);
     int rc;
-    if ((rc = d_text.alloc((size_t)n * stride * 4)) || (rc = d_meta.alloc(meta.size() * 4)) || (rc = d_tot.alloc(sizeof(NNPlanTotals))) ||
-        (rc = d_chunks.alloc((size_t)(2 * cap_in + 2 * cap_out) * sizeof(NNChunk))) || (rc = d_list.alloc((size_t)total * 4)) || (rc = d_pa.alloc((size_t)total * 4)) ||
+    if ((rc = d_text.alloc((size_t)n * stride * 4)) || (rc = d_meta.upload(meta.data(), meta.size() * 4)) || (rc = d_tot.upload(&tot, sizeof(tot))) ||
+        (rc = d_chunks.alloc((size_t)(2 * cap_in + 2 * cap_out) * sizeof(NNChunk))) || (rc = d_list.upload(words, (size_t)total * 4)) || (rc = d_pa.alloc((size_t)total * 4)) ||
         (rc = d_pb.alloc((size_t)total * 4)) || (rc = d_tasks.alloc((size_t)std::max<uint64_t>(tasks_cap, 1) * sizeof(NNFTask))))
         return rc;
-    ISO_HIP_CHECK(copy_h2d(d_meta.p, meta.data(), meta.size() * 4));
-    ISO_HIP_CHECK(copy_h2d(d_tot.p, &tot, sizeof(tot)));
     ISO_HIP_CHECK(copy_h2d(d_chunks.p, chunks.data(), chunks.size() * sizeof(NNChunk)));
-    ISO_HIP_CHECK(copy_h2d(d_list.p, words, (size_t)total * 4));
     NNChunk *left = d_chunks.as<NNChunk>() + 2 * cap_in;
     hipLaunchKernelGGL(k_build_text2, dim3(n), dim3(256), 0, 0, s->dev, d_text.as<uint32_t>(), stride);
     ISO_HIP_CHECK(hipGetLastError());
