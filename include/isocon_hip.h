@@ -156,6 +156,27 @@ int isocon_block_filter_chunks(isocon_store *s, const int32_t *thr, uint32_t n_c
 int isocon_qgram_bound_matrix(isocon_store *s, uint32_t q_begin, uint32_t q_end, uint32_t q_stride, uint32_t q_block, uint64_t depth,
                               uint64_t *out_row_ptr, uint8_t *out_bounds, uint64_t bounds_cap, uint64_t *n_bounds_needed);
 
+/*
+ * What the bound kernel leaves BESIDE that matrix for a search over the shard with the roles is_converged / is_target (each may be NULL,
+ * as for isocon_nn_graph) and the seed pairs proposed from it, read back raw for tests: the launches are the search's own up to the
+ * proposal of the seed pairs; no pair is aligned.  The reference has no counterpart.  With rows = the entries of the shard and
+ * S = out_params[0]:
+ *   out_score[n]               hub scores: window pairs with a bound <= out_params[1] that have the entry at either end
+ *   out_rowmin[rows * S]       per row and class c of column tiles ((p / out_params[2]) % S == c): the smallest (bound, column) over the
+ *                              row's admissible columns as bound << 32 | (p - q - 1); all ones: none
+ *   out_colmin[n * S]          per entry p and class c of ROW tiles ((slot / out_params[2]) % S == c): the smallest (bound, row entry) over
+ *                              the admissible rows whose window holds p as bound << 32 | q; all ones: none
+ *   out_pa, out_pb[2 * S * n]  the proposed pairs, *out_count of them in no defined order, 0xffffffff behind them
+ *   out_known[n * 2 * S]       per entry the other ends of the pairs it proposed, in the order it proposed them, then 0xffffffff
+ *   out_params[4]              S (seed classes), the hub bound, the tile size, and the number of merged column classes of the proposal
+ * With every output but out_params NULL the call only fills out_params[0 .. 2] (the sizes above).  ISOCON_E_UNSUPPORTED: no room for
+ * the matrix, the minima or the table of the seed pairs.  Argument and alphabet errors as isocon_qgram_bound_matrix.
+ */
+int isocon_qgram_seed_tables(isocon_store *s, const uint8_t *is_converged, const uint8_t *is_target, uint64_t depth,
+                             uint32_t q_begin, uint32_t q_end, uint32_t q_stride, uint32_t q_block,
+                             uint32_t *out_score, uint64_t *out_rowmin, uint64_t *out_colmin, uint32_t *out_pa, uint32_t *out_pb,
+                             uint64_t *out_count, uint32_t *out_known, uint32_t *out_params);
+
 /* statistics block filled by the nearest-neighbour entry points (all counters are for the one call) */
 typedef struct {
     uint64_t pairs_evaluated;     /* (shared,lane) pairs the banded kernels actually ran */

@@ -72,6 +72,8 @@ SYMBOLS = {
                                                   u64p, ctypes.c_uint64, u32p, ctypes.c_uint64, u32p, u32p, ctypes.c_uint64, u64p]),
     "isocon_qgram_bound_matrix": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, u64p, u8p,
                                                  ctypes.c_uint64, u64p]),
+    "isocon_qgram_seed_tables": (ctypes.c_int, [ctypes.c_void_p, u8p, u8p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                u32p, u64p, u64p, u32p, u32p, u64p, u32p, u32p]),
     "isocon_nn_graph": (ctypes.c_int, [ctypes.c_void_p, u8p, u8p, ctypes.c_uint64, i32p, u64p, u32p, ctypes.c_uint64,
                                        u64p, ctypes.POINTER(NNStats)]),
     "isocon_nn_partial": (ctypes.c_int, [ctypes.c_void_p, u8p, u8p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,

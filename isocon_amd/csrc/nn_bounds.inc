@@ -1,4 +1,4 @@
-// nn_bounds.inc -- NNContext::build_bounds (q-gram profiles, row layouts, tile table, k_qgram_mm) and NNContext::run_bound_seeds (the smallest-bound pairs aligned first) (included by isocon_hip.hip behind nn_context.inc).
+// nn_bounds.inc -- NNContext::build_bounds (q-gram profiles, row layouts, tile table, k_qgram_mm) and NNContext::run_bound_seeds (the smallest-bound pairs proposed and aligned first) (included by isocon_hip.hip behind nn_context.inc).
 
 namespace {
 
@@ -257,13 +257,10 @@ int NNContext::build_bounds(const QMap &Q, int32_t kcap, NNParams &P, bool want_
     return ISOCON_OK;
 }
 
-// Exact distances of every entry's smallest-bound pairs (one pair per lane, ed_lanes.hpp) through the update rule of the
-// search: best[] starts the main pass close to its final values.
-int NNContext::run_bound_seeds(const QMap &Q)
+// The seed pairs of the shard from the row / column minima build_bounds left (k_qgram_seed_pairs): appended to d_seed_a / d_seed_b, counted in
+// d_seed_n, each entry's pairs in its row of the known table.  classes_used: the col_classes of the launch.
+int NNContext::propose_bound_seeds(const QMap &Q, uint32_t *classes_used)
 {
-    if (!seeds_ready) return ISOCON_OK;
-    tm.start();
-    const uint64_t np = (uint64_t)2 * QM_SEEDS * n;
     // a shard that owns 1 / N of the rows merges its column candidates into QM_SEEDS / N classes (k_qgram_seed_pairs)
     const uint32_t ranks = std::max<uint32_t>(1u, Q.stride >> Q.block_log2);
     uint32_t col_classes = QM_SEEDS;
@@ -273,9 +270,28 @@ int NNContext::run_bound_seeds(const QMap &Q)
     hipLaunchKernelGGL(k_qgram_seed_pairs, dim3((n + 255) / 256), dim3(256), 0, 0, d_rowmin.as<unsigned long long>(), d_colmin.as<unsigned long long>(),
                        n, Q, seed_nq, col_classes, d_seed_a.as<uint32_t>(), d_seed_b.as<uint32_t>(), d_seed_n.as<unsigned long long>(), d_known.as<uint32_t>());
     ISO_HIP_CHECK(hipGetLastError());
+    if (classes_used) *classes_used = col_classes;
+    return ISOCON_OK;
+}
+
+// Exact distances of the proposed pairs (one pair per lane, ed_lanes.hpp) through the update rule of the search: best[] starts the main
+// pass close to its final values.
+int NNContext::align_bound_seeds()
+{
+    const uint64_t np = (uint64_t)2 * QM_SEEDS * n;
     hipLaunchKernelGGL(k_ed_lanes<true>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, 0, st->dev, params(63), d_seed_a.as<uint32_t>(), d_seed_b.as<uint32_t>(),
                        (const int32_t *)nullptr, np, (int32_t *)nullptr);
     ISO_HIP_CHECK(hipGetLastError());
+    return ISOCON_OK;
+}
+
+// Every entry's smallest-bound pairs aligned first: the proposal, then the alignment.
+int NNContext::run_bound_seeds(const QMap &Q)
+{
+    if (!seeds_ready) return ISOCON_OK;
+    tm.start();
+    int rc;
+    if ((rc = propose_bound_seeds(Q)) || (rc = align_bound_seeds())) return rc;
     tm.stop_later(&stats.seed_kernel_ms);
     known_ready = d_known.p != nullptr;          // (every pair in the table is in the launch above)
     return ISOCON_OK;

@@ -136,7 +136,9 @@ struct NNContext {
     unsigned long long lb_total = 0;
     bool seeds_ready = false;
     uint32_t seed_nq = 0;
-    int run_bound_seeds(const QMap &Q);          // nn_bounds.inc
+    int run_bound_seeds(const QMap &Q);          // nn_bounds.inc: propose_bound_seeds, then align_bound_seeds
+    int propose_bound_seeds(const QMap &Q, uint32_t *classes_used = nullptr);
+    int align_bound_seeds();
     // The table of the seed pairs (NNSeedKnown, nn_list.hpp): known_ready from the launch of THIS pass' seed pairs (run_bound_seeds) to the
     // next start of a pass (begin_pass: best[] is uploaded again, the hit list starts over) -- never across calls.  The kernels that make
     // flat pairs get it only where its argument holds as it is written down: one set with every entry query and target, thresholds that

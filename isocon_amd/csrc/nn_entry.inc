@@ -339,3 +339,66 @@ extern "C" int isocon_qgram_bound_matrix(isocon_store *s, uint32_t q_begin, uint
     return ISOCON_OK;
 }
 
+
+// What the epilogue of k_qgram_mm and k_qgram_seed_pairs leave beside the matrix for a search over this shard with these roles, read back
+// raw: hub scores, row / column minima, the proposed seed pairs with their counter and the table of the seed pairs.  The launches are the
+// search's own up to the proposal (NNContext::propose_bound_seeds); no pair is aligned.  Tests compare every word with a restatement.
+extern "C" int isocon_qgram_seed_tables(isocon_store *s, const uint8_t *is_converged, const uint8_t *is_target, uint64_t depth,
+                                        uint32_t q_begin, uint32_t q_end, uint32_t q_stride, uint32_t q_block,
+                                        uint32_t *out_score, uint64_t *out_rowmin, uint64_t *out_colmin, uint32_t *out_pa, uint32_t *out_pb,
+                                        uint64_t *out_count, uint32_t *out_known, uint32_t *out_params)
+{
+    if (!s || !out_params || !qmap_args_ok(q_stride, q_block)) return ISOCON_E_ARG;
+    out_params[0] = (uint32_t)QM_SEEDS; out_params[1] = QM_HUB_BOUND; out_params[2] = (uint32_t)QM_TILE; out_params[3] = 0u;
+    const bool sizing = !out_score && !out_rowmin && !out_colmin && !out_pa && !out_pb && !out_count && !out_known;
+    if (sizing) return ISOCON_OK;          // (the constants that size the arrays of the call proper)
+    if (!out_score || !out_rowmin || !out_colmin || !out_pa || !out_pb || !out_count || !out_known) return ISOCON_E_ARG;
+    if (s->n_exc) { g_last_error = "q-gram bounds are defined on the 2-bit planes: the set holds more than four distinct symbols"; return ISOCON_E_ALPHABET; }
+    const uint32_t n = s->dev.n;
+    if (q_end > n) q_end = n;
+    NNContext C;
+    int rc = nn_setup(C, s, is_converged, is_target, depth, nullptr);
+    if (rc) return rc;
+    if ((rc = C.flush_flags())) return rc;          // (both role arrays are on the device before k_qgram_mm reads them)
+    NNParams P = C.params(63);
+    s->pool.bound_tag.valid = false;
+    const QMap Q = qmap_of(q_begin, q_end, q_stride, q_block);
+    const uint32_t nq = Q.count();
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the minima travel as they are");
+    const size_t n_seed_words = (size_t)2 * QM_SEEDS * n;
+    rc = C.build_bounds(Q, 63, P, true);
+    s->pool.bound_tag.valid = false;
+    if (rc) return rc;
+    if (!C.seeds_ready) {
+        // no pair inside the window: every table keeps its fill.  Anything else: no room for the matrix or for the minima.
+        bool any = false;
+        for (uint32_t r = 0; r < C.lb_len_host.size(); ++r) any = any || C.lb_len_host[r] != 0;
+        if (any || P.lb != nullptr) { g_last_error = "seed tables not built (memory)"; return ISOCON_E_UNSUPPORTED; }
+        ISO_HIP_CHECK(device_wait());
+        C.tm.resolve();
+        std::fill(out_score, out_score + n, 0u);
+        std::fill(out_rowmin, out_rowmin + (size_t)nq * QM_SEEDS, ~(uint64_t)0);
+        std::fill(out_colmin, out_colmin + (size_t)n * QM_SEEDS, ~(uint64_t)0);
+        std::fill(out_pa, out_pa + n_seed_words, 0xffffffffu);
+        std::fill(out_pb, out_pb + n_seed_words, 0xffffffffu);
+        std::fill(out_known, out_known + (size_t)n * NN_KNOWN_SLOTS, 0xffffffffu);
+        *out_count = 0;
+        out_params[3] = (uint32_t)QM_SEEDS;
+        return ISOCON_OK;
+    }
+    if (C.d_known.p == nullptr) { g_last_error = "no room for the table of the seed pairs"; return ISOCON_E_UNSUPPORTED; }
+    C.tm.start();
+    rc = C.propose_bound_seeds(Q, &out_params[3]);
+    C.tm.stop_later(&C.stats.seed_kernel_ms);
+    if (rc) return rc;
+    ISO_HIP_CHECK(device_wait());
+    C.tm.resolve();
+    ISO_HIP_CHECK(copy_d2h(out_score, C.d_score.p, (size_t)n * 4));
+    if (nq) ISO_HIP_CHECK(copy_d2h(out_rowmin, C.d_rowmin.p, (size_t)nq * QM_SEEDS * 8));
+    ISO_HIP_CHECK(copy_d2h(out_colmin, C.d_colmin.p, (size_t)n * QM_SEEDS * 8));
+    ISO_HIP_CHECK(copy_d2h(out_pa, C.d_seed_a.p, n_seed_words * 4));
+    ISO_HIP_CHECK(copy_d2h(out_pb, C.d_seed_b.p, n_seed_words * 4));
+    ISO_HIP_CHECK(copy_d2h(out_count, C.d_seed_n.p, 8));
+    ISO_HIP_CHECK(copy_d2h(out_known, C.d_known.p, (size_t)n * NN_KNOWN_SLOTS * 4));
+    return ISOCON_OK;
+}

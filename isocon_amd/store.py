@@ -243,6 +243,36 @@ class SeqStore(object):
             _lib.check(rc, "isocon_qgram_bound_matrix")
             return row_ptr, out[:int(row_ptr[-1])]
 
+    def qgram_seed_tables(self, is_converged=None, is_target=None, q_begin=0, q_end=None, q_stride=1, depth=2 ** 32, q_block=1):
+        """What the bound kernel leaves beside the matrix for a search over the shard with these roles, and the seed pairs proposed from
+        it, read back raw (isocon_qgram_seed_tables; tests).  A dict: `score` uint32[n], `rowmin` uint64[rows, seeds], `colmin`
+        uint64[n, seeds], `pa`, `pb` uint32[2 * seeds * n] (whole arrays), `count`, `known` uint32[n, 2 * seeds], and the parameters
+        `seeds`, `hub_bound`, `tile`, `col_classes`."""
+        n = self.n
+        q_end = n if q_end is None else min(int(q_end), n)
+        conv = None if is_converged is None else np.ascontiguousarray(is_converged, dtype=np.uint8)
+        targ = None if is_target is None else np.ascontiguousarray(is_target, dtype=np.uint8)
+        if (conv is not None and len(conv) != n) or (targ is not None and len(targ) != n):
+            raise ValueError("one role flag per entry")
+        depth = int(min(depth, 2 ** 63 - 1))
+        params = np.zeros(4, dtype=np.uint32)
+        args = (self._h, _ptr(conv, _lib.u8p), _ptr(targ, _lib.u8p), depth, q_begin, q_end, q_stride, q_block)
+        _lib.check(self._L.isocon_qgram_seed_tables(*(args + (None,) * 7 + (_ptr(params, _lib.u32p),))), "isocon_qgram_seed_tables")
+        seeds = int(params[0])
+        rows = len(shard_entries(q_begin, q_end, q_stride, q_block))
+        score = np.zeros(max(n, 1), dtype=np.uint32)
+        rowmin = np.zeros((max(rows, 1), seeds), dtype=np.uint64)
+        colmin = np.zeros((max(n, 1), seeds), dtype=np.uint64)
+        pa = np.zeros(max(2 * seeds * n, 1), dtype=np.uint32)
+        pb = np.zeros(max(2 * seeds * n, 1), dtype=np.uint32)
+        count = np.zeros(1, dtype=np.uint64)
+        known = np.zeros((max(n, 1), 2 * seeds), dtype=np.uint32)
+        _lib.check(self._L.isocon_qgram_seed_tables(*(args + (_ptr(score, _lib.u32p), _ptr(rowmin, _lib.u64p), _ptr(colmin, _lib.u64p), _ptr(pa, _lib.u32p),
+                                                              _ptr(pb, _lib.u32p), _ptr(count, _lib.u64p), _ptr(known, _lib.u32p), _ptr(params, _lib.u32p)))),
+                   "isocon_qgram_seed_tables")
+        return {"score": score[:n], "rowmin": rowmin[:rows], "colmin": colmin[:n], "pa": pa[:2 * seeds * n], "pb": pb[:2 * seeds * n], "count": int(count[0]),
+                "known": known[:n], "seeds": seeds, "hub_bound": int(params[1]), "tile": int(params[2]), "col_classes": int(params[3])}
+
     def hw_pairs(self, q, t, k, return_ms=False, reuse_buffer=False, wide=False):
         """Infix (edlib "HW", task="path") alignment of sequence q[p] inside sequence t[p] with threshold k[p]:
         int32 [n, 5] = distance (-1 if > k), start, end, leading insertion run, trailing insertion run

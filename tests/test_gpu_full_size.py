@@ -82,7 +82,8 @@ def test_c3_pruning_counters(c3):
     built, hub scores and seed keys come out of the bound kernel's epilogue) and have been the same through every rewrite of that epilogue
     (profiles/r06j_bench.json).  A change of the seeds, of the hub scores that decide which end owns a pair, of either bound or of a
     threshold moves them without touching the graph -- this is where it shows.  A DELIBERATE change of a tuning constant (bins, gram
-    length, probe stride) updates the numbers here."""
+    length, probe stride) updates the numbers here.  The comparison of every hub score, row / column minimum and seed pair with a
+    restatement lives in tests/test_gpu_qgram_seed_tables.py (a designed set of 1 600 entries); these counters remain the full-size pin."""
     seqs, st, best, row_ptr, cols, stats = c3
     assert int(stats["pairs_prefiltered"]) == 293119143          # window pairs rejected by the q-gram bound
     assert int(stats["pairs_block_rejected"]) == 13913023        # survivors rejected by the block bound (both passes)
