@@ -147,6 +147,19 @@ int isocon_block_filter_chunks(isocon_store *s, const int32_t *thr, uint32_t n_c
                                uint64_t *out_counters);
 
 /*
+ * The block test of the depth-limited 2-set search (csrc/nn2_depth.hpp: k_nn2_block_reject) on pairs the caller made (tests): the kernel
+ * and its launch are the search's own.  Pair p = (read[p], target[p]) with threshold k[p]; runs of equal read[] are one read's pairs of a
+ * round and are cut into tasks of at most 64 pairs, a wave each (the search itself lists at most 33 per read and round).
+ * out_rejected[p] = 1 iff the pair is tested and isocon_block_bound_pairs(read[p], target[p], probe_stride) > k[p] -- its distance then
+ * exceeds k[p] --, else 0.  Not tested: k[p] < 0 (how the search marks a pair outside the planes' map), a pair with a sequence that holds
+ * symbols outside the 2-bit map (whatever k[p]; no ISOCON_E_ALPHABET), and k[p] >= len(target[p]) / 8 (the count cannot exceed it).
+ * *kernel_ms (may be NULL): HIP-event time of the test's launch.  ISOCON_E_ARG: an index >= the store's size, probe_stride other than 2
+ * or 4, 2^31 pairs or more.  The reference has no counterpart: it aligns these pairs and gets -1 (modules/nearest_neighbor_graph.py:341-424).
+ */
+int isocon_nn2_block_reject(isocon_store *s, const uint32_t *read, const uint32_t *target, const int32_t *k, uint64_t n_pairs, int32_t probe_stride,
+                            uint8_t *out_rejected, float *kernel_ms);
+
+/*
  * The bound matrix the main pass of isocon_nn_graph / isocon_nn_partial consults for the shard (q_begin, q_end, q_stride, q_block) --
  * see isocon_nn_partial -- of a length-sorted store, read back for tests: row r belongs to the shard's r-th entry q, its bytes
  * out_bounds[out_row_ptr[r] .. out_row_ptr[r + 1]) are min(255, bound) of the pairs (q, p), p = q + 1, q + 2, ... while
@@ -219,8 +232,14 @@ typedef struct {
  *     depth >= the number of targets (the reference's default 2**32) never binds.  A smaller depth is the reference's rule (:416): a
  *     read stops after the iteration in which its count of candidate alignments reaches depth (depth + 1 alignments at most, depth 0 =
  *     one iteration), candidates visited by ascending offset, the lower one first -- carried out on the device round by round.
- *     stats on that path: kernel_ms, hits, pairs_lanes = distinct (read, candidate) pairs whose distance was asked for, full_pairs,
- *     pairs_bytes, scan_launches = rounds.
+ *     Under ISOCON_DEBUG_VARIANT=nn2_block_filter (off by default: it costs more than it saves, profiles/nn2set_depth.txt; off under
+ *     nn_no_block_filter in any case) a listed pair whose block bound (isocon_block_bound_pairs, stride 2) exceeds its threshold is
+ *     final with the -1 edlib would give and is not aligned (csrc/nn2_depth.hpp, k_nn2_block_reject): same rows.
+ *     stats on that path: kernel_ms, hits, pairs_lanes = distinct (read, candidate) pairs whose distance was asked for (the same with
+ *     and without the block test), pairs_block_rejected = of those, pairs the block test decided, pairs_lanes_aligned = pairs handed to
+ *     the one-pair-per-lane launch (pairs_lanes - pairs_block_rejected), filter_kernel_ms = HIP-event time of the test's launches
+ *     (2-bit texts, test, compaction, scatter; part of kernel_ms), full_pairs, pairs_bytes (never tested, never rejected),
+ *     scan_launches = rounds.
  * Output CSR: out_best[i] = minimal distance (-1 if row empty), out_row_ptr[n+1], out_cols = neighbour indices in
  * the reference's insertion order (ascending offset, lower index first).  If the edges do not fit cols_cap the
  * call returns ISOCON_E_CAPACITY and *n_cols_needed holds the required capacity.

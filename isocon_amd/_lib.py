@@ -70,6 +70,7 @@ SYMBOLS = {
     "isocon_block_bound_pairs": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, ctypes.c_uint64, ctypes.c_int32, i32p]),
     "isocon_block_filter_chunks": (ctypes.c_int, [ctypes.c_void_p, i32p, ctypes.c_uint32, u32p, u8p, u64p, u32p, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int32, u32p, u32p,
                                                   u64p, ctypes.c_uint64, u32p, ctypes.c_uint64, u32p, u32p, ctypes.c_uint64, u64p]),
+    "isocon_nn2_block_reject": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, i32p, ctypes.c_uint64, ctypes.c_int32, u8p, f32p]),
     "isocon_qgram_bound_matrix": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, u64p, u8p,
                                                  ctypes.c_uint64, u64p]),
     "isocon_qgram_seed_tables": (ctypes.c_int, [ctypes.c_void_p, u8p, u8p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,

@@ -131,4 +131,54 @@ ISO_HD void nn2_replay(const NN2Set &S, uint32_t i, uint32_t ti, NN2Lane &L, uin
     }
 }
 
+// Between steps 1 and 2 the block bound of nn_filter.hpp looks at the listed pairs (k_nn2_block_reject, nn2_depth.hpp): a pair whose
+// greedy count of disjoint 8-grams of the target that occur nowhere in the read exceeds k has a distance above k, i.e. the -1 its slot
+// already holds.  A wave takes a TASK: up to NN2_TASK_PAIRS consecutive pairs of one read's run in the pair arrays.
+static constexpr uint32_t NN2_TASK_PAIRS = 64;
+static constexpr int32_t NN2_REJECTED = -2;          // pk_lanes of a pair the block bound has decided (-1: an entry outside the planes' map)
+static constexpr int NN2_PROBE_STRIDE = 2;           // bases between two probes of the test (2 or 4; profiles/nn2set_depth.txt)
+
+struct NN2Task { uint32_t read, count; unsigned long long begin; };
+
+// Whether the test looks at a pair: k = its threshold for the 64-row kernel (negative: not for the bit-vector kernels), len_t = the
+// target's length.  A target holds at most len_t / 8 disjoint 8-grams, so with k >= len_t / 8 the count cannot exceed k.
+ISO_HD bool nn2_tested(int32_t k, int32_t len_t) { return k >= 0 && k < len_t / 8; }
+
+// Cuts the run [begin, begin + count) of one read's pairs into tasks: emit(first, pairs) for ranges of at most NN2_TASK_PAIRS pairs
+// that start and end with a tested pair and together hold every tested pair once (tested(p): pair p is one); untested pairs in
+// between ride along as idle lanes.  A run without a tested pair makes no task.  Returns the number of tasks.
+template <class Tested, class Emit>
+ISO_HD uint32_t nn2_cut_tasks(unsigned long long begin, unsigned long long count, Tested tested, Emit emit)
+{
+    const unsigned long long end = begin + count;
+    uint32_t n_tasks = 0;
+    unsigned long long p = begin;
+    for (;;) {
+        while (p < end && !tested(p)) ++p;
+        if (p >= end) break;
+        const unsigned long long stop = end - p > NN2_TASK_PAIRS ? p + NN2_TASK_PAIRS : end;
+        unsigned long long last = p;
+        for (unsigned long long t = p + 1; t < stop; ++t)
+            if (tested(t)) last = t;
+        emit(p, (uint32_t)(last - p + 1));
+        ++n_tasks;
+        p = last + 1;
+    }
+    return n_tasks;
+}
+
+// A whole pair list whose runs of equal read[] are the reads' runs (the test entry isocon_nn2_block_reject; the search's listing kernel
+// knows its run and calls nn2_cut_tasks itself): emit(read, first, pairs) per task.  Returns the number of tasks.
+template <class Tested, class Emit>
+inline unsigned long long nn2_cut_list(const uint32_t *read, unsigned long long n_pairs, Tested tested, Emit emit)
+{
+    unsigned long long n_tasks = 0;
+    for (unsigned long long b = 0, e; b < n_pairs; b = e) {
+        for (e = b + 1; e < n_pairs && read[e] == read[b]; ++e) {}
+        const uint32_t x = read[b];
+        n_tasks += nn2_cut_tasks(b, e - b, tested, [&](unsigned long long first, uint32_t pairs) { emit(x, first, pairs); });
+    }
+    return n_tasks;
+}
+
 }  // namespace isocon

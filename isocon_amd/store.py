@@ -192,6 +192,20 @@ class SeqStore(object):
         _lib.check(self._L.isocon_block_bound_pairs(self._h, _ptr(a, _lib.u32p), _ptr(b, _lib.u32p), len(a), probe_stride, _ptr(out, _lib.i32p)), "isocon_block_bound_pairs")
         return out
 
+    def nn2_block_reject(self, read, target, k, probe_stride=2):
+        """The block test of the depth-limited 2-set search on caller-made pairs (isocon_nn2_block_reject; tests): runs of equal read[] are
+        one read's pairs, k[p] the pair's threshold (negative: not tested).  Returns a uint8 array: 1 where the block bound of the pair
+        exceeds k[p] -- its edit distance then does too."""
+        a = np.ascontiguousarray(read, dtype=np.uint32)
+        b = np.ascontiguousarray(target, dtype=np.uint32)
+        kk = np.ascontiguousarray(k, dtype=np.int32)
+        if len(a) != len(b) or len(a) != len(kk):
+            raise ValueError("pair arrays differ in length")
+        out = np.zeros(len(a), dtype=np.uint8)
+        _lib.check(self._L.isocon_nn2_block_reject(self._h, _ptr(a, _lib.u32p), _ptr(b, _lib.u32p), _ptr(kk, _lib.i32p), len(a), int(probe_stride),
+                                                   _ptr(out, _lib.u8p), None), "isocon_nn2_block_reject")
+        return out
+
     def block_filter_chunks(self, thr, owner, narrow, chunk_ptr, words, kcap, list_min, second_pass):
         """The main pass's two filter kernels on caller-made chunks (isocon_block_filter_chunks; tests).  thr[n]: per-entry thresholds 0 .. 64;
         chunk c: owner[c], narrow[c], list words words[chunk_ptr[c]:chunk_ptr[c + 1]].  Returns a dict: `chunks` -- what is left for the tables,
