@@ -430,6 +430,18 @@ int isocon_hw_pairs(isocon_store *s, const uint32_t *q, const uint32_t *t, const
                     int32_t *out, float *kernel_ms);
 
 /*
+ * Which route and band classes the calling thread's last isocon_hw_pairs call took (no counterpart in the reference; tests).
+ * out[0] route (0: tiles built on the host, 1: on the device); out[1] 1 if the call fell back from device tiles to host tiles;
+ * out[2] pairs of the call; out[3] pairs that needed a kernel; out[4] hits; out[5..8] LOCATE tiles of the classes of 1, 2, 4 and 8
+ * window words (64, 128, 256, 512 diagonals; on the device route a tile is filed under the class of its COMMON window);
+ * out[9..12] START + TRACE tiles per class; out[13..16] the grid each of those launches got (fewer workgroups than tiles: a
+ * workgroup ran several tiles on one store).  isocon_hw_pairs zeroes the values when it is called.  isocon_hw_window_graph and
+ * isocon_hw_path_pairs run the device route on lists of their own and leave its counters here, with out[3] = out[4] = -1 (not
+ * counted).  Writes min(cap, 17) values and returns that number.
+ */
+int isocon_hw_last_stats(double *out, int32_t cap);
+
+/*
  * isocon_hw_pairs without the limit of 512 diagonals: the same arguments, checks and (n_pairs, 5) output, for any k[p] <= 2^20 --
  * edlib_traceback (modules/end_invariant_functions.py:593-620) with k >= 256, and get_all_NN (:661, :668: k = 10 + ignore_ends_len over
  * a length window of 10 + 2 ignore_ends_len) with ignore_ends_len >= 121.  Every pair is classed on the host from the two lengths and

@@ -109,6 +109,7 @@ SYMBOLS = {
     "isocon_msa_correct": (ctypes.c_int, [u8p, ctypes.c_uint32, ctypes.c_uint32, i32p, u8p, ctypes.c_uint64, u64p, i32p,
                                           ctypes.POINTER(ctypes.c_int64), f32p]),
     "isocon_hw_pairs": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, i32p, ctypes.c_uint64, i32p, f32p]),
+    "isocon_hw_last_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.c_int32]),
     "isocon_hw_pairs_wide": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, i32p, ctypes.c_uint64, i32p, f32p]),
     "isocon_hw_window_graph": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                               u64p, u32p, i32p, ctypes.c_uint64, u64p, u64p, f32p]),

@@ -5,6 +5,17 @@ namespace {
 
 inline int hw_words(int32_t rows) { return rows <= 64 ? 1 : rows <= 128 ? 2 : rows <= 256 ? 4 : rows <= 512 ? 8 : 0; }
 
+// isocon_hw_last_stats: the calling thread's last isocon_hw_pairs call (and what hw_pairs_device_core did for the entries that share it).
+// HS_LOCATE / HS_FINISH / HS_GRID + c: class c = 0 .. 3 (1, 2, 4, 8 window words).  -1: not counted on that route.
+enum { HS_ROUTE = 0, HS_RETRIED_HOST, HS_PAIRS, HS_NEED_KERNEL, HS_HITS, HS_LOCATE, HS_FINISH = HS_LOCATE + 4, HS_GRID = HS_FINISH + 4, HS_COUNT = HS_GRID + 4 };
+thread_local double g_hw_stats[HS_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+inline void hw_stats_route(int route, uint64_t n_pairs)
+{
+    for (int i = 0; i < HS_COUNT; ++i) if (route == 1 || i != HS_RETRIED_HOST) g_hw_stats[i] = 0;          // (the host route may be the retry)
+    g_hw_stats[HS_ROUTE] = route;
+    g_hw_stats[HS_PAIRS] = (double)n_pairs;
+}
+
 // Tiles of the pairs `idx` (any order): pairs are grouped by (words needed, query) with two counting sorts, a group is cut
 // into tiles of at most 64 lanes whose COMMON window (largest length difference and largest threshold of the tile) still
 // fits the class.  rows(p) = rows of the band pair p needs on its own; fits(dmax, kmax, W) = do these extremes fit W words.
@@ -83,6 +94,7 @@ int hw_pairs_host_tiles(isocon_store *s, const uint32_t *q, const uint32_t *t, c
 {
     const uint32_t n = s->dev.n;
     const std::vector<int32_t> &lens = s->lens;
+    hw_stats_route(0, n_pairs);
     // pairs that need no kernel (distance >= len(q) - len(t) > k, or an empty sequence) and the band every other pair needs
     std::vector<uint32_t> run;
     run.reserve(n_pairs);
@@ -101,6 +113,7 @@ int hw_pairs_host_tiles(isocon_store *s, const uint32_t *q, const uint32_t *t, c
         }
         run.push_back((uint32_t)p);
     }
+    g_hw_stats[HS_NEED_KERNEL] = (double)run.size();
     if (run.empty()) return ISOCON_OK;
     HostClock clk;
     clk.lap("hw: classify");
@@ -134,6 +147,7 @@ int hw_pairs_host_tiles(isocon_store *s, const uint32_t *q, const uint32_t *t, c
                        }, tiles);
         clk.lap("hw: locate tiles (host)");
         for (int c = 0; c < 4; ++c) {
+            g_hw_stats[HS_LOCATE + c] = (double)tiles.tile_q[c].size();
             if (tiles.tile_q[c].empty()) continue;
             HwTileIn in{};
             if ((rc = upload_tiles(tiles.tile_q[c], tiles.lane_pair[c], in))) return rc;
@@ -155,6 +169,7 @@ int hw_pairs_host_tiles(isocon_store *s, const uint32_t *q, const uint32_t *t, c
     }
     if (clk.on) fprintf(stderr, "[isocon] hw: %zu pairs, %zu need a kernel, %zu hits\n", (size_t)n_pairs, run.size(), hits.size());
     clk.lap("hw: he download + hit list");
+    g_hw_stats[HS_HITS] = (double)hits.size();
     if (hits.empty()) { if (kernel_ms) *kernel_ms = tm.total; return ISOCON_OK; }
     // ---- START + TRACE + walk for the hits: smallest start, terminal insertion runs ----
     if ((rc = d_out.alloc(n_pairs * 20))) return rc;
@@ -171,6 +186,7 @@ int hw_pairs_host_tiles(isocon_store *s, const uint32_t *q, const uint32_t *t, c
         clk.lap("hw: finish tiles (host)");
         const uint32_t trace_cols = (uint32_t)s->maxlen + 1;
         for (int c = 0; c < 4; ++c) {
+            g_hw_stats[HS_FINISH + c] = (double)tiles.tile_q[c].size();
             if (tiles.tile_q[c].empty()) continue;
             const int Wc = 1 << c;
             HwTileIn in{};
@@ -181,6 +197,7 @@ int hw_pairs_host_tiles(isocon_store *s, const uint32_t *q, const uint32_t *t, c
             uint64_t budget = (uint64_t)12 << 30;
             if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = std::min<uint64_t>(budget, (uint64_t)free_b / 3);
             const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(in.n_tiles, hw_finish_grid_cap(Wc)), budget / per_block));
+            g_hw_stats[HS_GRID + c] = (double)grid;
             if ((rc = d_trace.alloc((size_t)grid * per_block))) return rc;
             tm.start();
             rc = c == 0 ? hw_launch_finish<1>(s, in, grid, d_he.as<int32_t>(), d_trace.as<uint64_t>(), trace_cols, d_out.as<int32_t>())
@@ -233,6 +250,8 @@ int hw_pairs_device_core(isocon_store *s, const uint32_t *d_q, const uint32_t *d
 {
     *retry_host = false;
     const uint32_t n = s->dev.n;
+    hw_stats_route(1, n_pairs);
+    g_hw_stats[HS_NEED_KERNEL] = g_hw_stats[HS_HITS] = -1;          // (counted by hw_pairs_device_tiles, which has the lists on the host)
     if ((uint64_t)n * 4 >= 0xfffffff0ull) { *retry_host = true; return ISOCON_E_UNSUPPORTED; }
     HostClock clk;
     ScratchPool *pl = &g_scratch;
@@ -277,6 +296,7 @@ int hw_pairs_device_core(isocon_store *s, const uint32_t *d_q, const uint32_t *d
     clk.lap("hw: locate tiles (device)");
     tm.start();
     for (int c = 0; c < 4; ++c) {
+        g_hw_stats[HS_LOCATE + c] = (double)ctr.cls[c];
         if (!ctr.cls[c]) continue;
         const HwTileIn in = tile_in(c, ctr);
         rc = c == 0 ? hw_launch_locate<1>(s, in, d_he.as<int32_t>()) : c == 1 ? hw_launch_locate<2>(s, in, d_he.as<int32_t>())
@@ -293,6 +313,7 @@ int hw_pairs_device_core(isocon_store *s, const uint32_t *d_q, const uint32_t *d
     clk.lap("hw: locate kernels + finish tiles (device)");
     const uint32_t trace_cols = (uint32_t)s->maxlen + 1;
     for (int c = 0; c < 4; ++c) {
+        g_hw_stats[HS_FINISH + c] = (double)ctr.cls[c];
         if (!ctr.cls[c]) continue;
         const int Wc = 1 << c;
         const HwTileIn in = tile_in(c, ctr);
@@ -301,6 +322,7 @@ int hw_pairs_device_core(isocon_store *s, const uint32_t *d_q, const uint32_t *d
         uint64_t budget = (uint64_t)12 << 30;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = std::min<uint64_t>(budget, (uint64_t)free_b / 3);
         const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(in.n_tiles, hw_finish_grid_cap(Wc)), budget / per_block));
+        g_hw_stats[HS_GRID + c] = (double)grid;
         if ((rc = d_trace.alloc((size_t)grid * per_block))) return rc;
         tm.start();
         rc = c == 0 ? hw_launch_finish<1>(s, in, grid, d_he.as<int32_t>(), d_trace.as<uint64_t>(), trace_cols, d_out.as<int32_t>())
@@ -336,14 +358,33 @@ int hw_pairs_device_tiles(isocon_store *s, const uint32_t *q, const uint32_t *t,
     if ((rc = hw_pairs_device_core(s, d_q.as<uint32_t>(), d_t.as<uint32_t>(), d_k.as<int32_t>(), n_pairs, &d_rows, kernel_ms, retry_host))) return rc;
     ISO_HIP_CHECK(copy_d2h(out, d_rows, n_pairs * 20));
     clk.lap("hw: results down");
+    // (isocon_hw_last_stats: the pairs the device classed as needing a kernel -- the rule of k_hwt_keys<0> -- and the hits among the rows)
+    const std::vector<int32_t> &lens = s->lens;
+    uint64_t need = 0, nhits = 0;
+    for (uint64_t p = 0; p < n_pairs; ++p) {
+        const int32_t lq = lens[q[p]], lt = lens[t[p]];
+        need += !(lt - lq < -k[p] || lq == 0 || lt == 0);
+        nhits += out[p * 5] >= 0;
+    }
+    g_hw_stats[HS_NEED_KERNEL] = (double)need;
+    g_hw_stats[HS_HITS] = (double)nhits;
     return ISOCON_OK;
 }
 
 }  // namespace
 
+extern "C" int isocon_hw_last_stats(double *out, int32_t cap)
+{
+    if (!out || cap < 0) return 0;
+    const int k = cap < (int)HS_COUNT ? cap : (int)HS_COUNT;
+    for (int i = 0; i < k; ++i) out[i] = g_hw_stats[i];
+    return k;
+}
+
 extern "C" int isocon_hw_pairs(isocon_store *s, const uint32_t *q, const uint32_t *t, const int32_t *k, uint64_t n_pairs,
                                int32_t *out, float *kernel_ms)
 {
+    for (double &x : g_hw_stats) x = 0;
     if (!s || (n_pairs && (!q || !t || !k || !out))) return ISOCON_E_ARG;
     if (kernel_ms) *kernel_ms = 0.f;
     if (!n_pairs) return ISOCON_OK;
@@ -353,6 +394,7 @@ extern "C" int isocon_hw_pairs(isocon_store *s, const uint32_t *q, const uint32_
         bool retry_host = false;
         const int rc = hw_pairs_device_tiles(s, q, t, k, n_pairs, out, kernel_ms, &retry_host);
         if (!retry_host) return rc;
+        g_hw_stats[HS_RETRIED_HOST] = 1;
         if (kernel_ms) *kernel_ms = 0.f;
     }
     return hw_pairs_host_tiles(s, q, t, k, n_pairs, out, kernel_ms);

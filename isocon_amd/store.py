@@ -609,6 +609,17 @@ def path_last_stats():
     return dict(zip(keys, list(out)))
 
 
+def hw_last_stats():
+    """which route and band classes this thread's most recent hw_pairs call took (isocon_hw_last_stats, include/isocon_hip.h): route
+    (0 host tiles, 1 device tiles), retried_host, pairs, need_kernel, hits, and per class of 1, 2, 4, 8 window words the LOCATE tiles,
+    the START + TRACE tiles and the grid of the latter's launch"""
+    out = (ctypes.c_double * 17)()
+    _lib.load().isocon_hw_last_stats(out, 17)
+    keys = ("route", "retried_host", "pairs", "need_kernel", "hits") + tuple(
+        "%s_w%d" % (name, w) for name in ("locate_tiles", "finish_tiles", "finish_grid") for w in (1, 2, 4, 8))
+    return {key: int(v) for key, v in zip(keys, out)}
+
+
 def shard_entries(q_begin, q_end, q_stride=1, q_block=1):
     """The entries a shard owns, in slot order (include/isocon_hip.h, isocon_nn_partial): q_begin <= x < q_end with
     (x - q_begin) mod q_stride < q_block."""
