@@ -416,6 +416,26 @@ int isocon_msa_correct_built_batch(isocon_store *s, uint32_t n_parts, uint32_t n
                                    uint8_t *out_packed, uint64_t packed_cap, uint64_t *out_offsets, int32_t *out_n_cand, float *kernel_ms);
 
 /*
+ * The two builds with the insertions of the wide slots PLACED ON THE DEVICE: get_best_solution (functions.py:635-676 with min_ed
+ * :771-799) for every slot whose longest insertion has at most 62 bases ('-' + longest + '-' then fits the 64 lanes of a wavefront;
+ * csrc/msa_place_core.hpp states the rule, k_msa_slot_rep / k_msa_place of csrc/msa.hpp apply it).  Arguments and refusals as
+ * isocon_msa_build_ops / isocon_msa_build_ops_batch without the record list: the list stays on the device (sized from the code-3 ops, so
+ * no capacity of it is the caller's business) and the placements are in the built matrix when the call returns.  What comes back are the
+ * records of the slots with a longest insertion beyond 62 bases only -- ALL records of such a slot, for the representative is picked from
+ * them -- in out_left (8 words each, the format of the builds above; *n_left of them, in no particular order; normally none), to be
+ * placed by the caller and sent as patches to isocon_msa_correct_built / isocon_msa_correct_built_batch, which pair with these builds
+ * as with the builds above (isocon_msa_read_built too).  *n_placed = records placed on the device (duplicates counted): *n_placed +
+ * *n_left is the *n_wide of the builds above.  ISOCON_E_CAPACITY if left_cap is too small: *n_left holds the count and the build STAYS
+ * (the matrix is complete but for the left-over records); the caller calls again for the list, which builds the same matrix again.
+ */
+int isocon_msa_build_ops_placed(isocon_store *s, uint32_t n_rows, const uint32_t *row_ids, const uint32_t *ops, const uint64_t *ops_ptr,
+                                uint32_t *out_n_cols, uint32_t *out_col_slot, uint32_t *out_longest, uint32_t *out_left, uint64_t left_cap,
+                                uint64_t *n_left, uint64_t *n_placed, float *kernel_ms);
+int isocon_msa_build_ops_placed_batch(isocon_store *s, uint32_t n_parts, const uint32_t *first_row, const uint32_t *row_ids, const uint32_t *ops,
+                                      const uint64_t *ops_ptr, uint32_t *out_n_cols, uint32_t *out_col_slot, uint32_t *out_longest, uint32_t *out_left,
+                                      uint64_t left_cap, uint64_t *n_left, uint64_t *n_placed, float *kernel_ms);
+
+/*
  * Batched infix ("HW") edit distance with location and path ends == edlib.align(q, t, mode="HW", task="path", k=k)
  * as consumed by edlib_traceback (modules/end_invariant_functions.py:593-620) inside get_all_NN (:622-681), the
  * candidate-vs-candidate graph of the statistical-test phase: the query is aligned globally inside the target, target

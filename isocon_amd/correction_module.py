@@ -15,6 +15,7 @@ from __future__ import annotations
 import numpy as np
 
 import ctypes
+import os
 
 from . import _lib
 from .functions import msa_matrix
@@ -174,10 +175,29 @@ def _wide_slot_patches(members, wide, col_slot, longest):
     return wide[:, 0], col_slot[slot], p_ptr.astype(np.uint32), sol_bytes[src]
 
 
+PLACE_STATS = {"calls": 0, "placed": 0, "left": 0}          # placed builds, wide-slot records placed on the device, records left to _wide_slot_patches
+
+
+def _device_place(st, method):
+    """do the wide-slot insertions of a build on `st` get their places on the device?  Not under ISOCON_DEBUG_VARIANT=msa_host_place (the
+    host route, for A/B runs), and not on a store object without the placed builds (stand-ins, derived stores): both keep the route on
+    which every record comes down and goes up again as a patch."""
+    if "msa_host_place" in {item.split("=")[0] for item in os.environ.get("ISOCON_DEBUG_VARIANT", "").split(",")}:
+        return False
+    return callable(getattr(st, method, None))
+
+
+def _count_placed(n_placed, left):
+    PLACE_STATS["calls"] += 1
+    PLACE_STATS["placed"] += int(n_placed)
+    PLACE_STATS["left"] += len(left)
+
+
 def _correct_partition_from_ops(batch, m, partition, seq_to_acc):
     """correct_to_consensus for a partition whose alignments are CIGAR ops on the device's store (isocon_get_candidates.AlignmentBatch):
-    the matrix is built there (isocon_msa_build_ops), the insertions of the wide slots are placed by get_best_solution here and sent
-    as patches, the correction runs on the built matrix (isocon_msa_correct_built).  Returns {accession: corrected sequence}."""
+    the matrix is built there with the insertions of its wide slots in place (isocon_msa_build_ops_placed; the records of a slot beyond
+    the 62 bases the device places are placed by get_best_solution here and sent as patches, like all records on the host route:
+    _device_place), the correction runs on the built matrix (isocon_msa_correct_built).  Returns {accession: corrected sequence}."""
     rows = batch.rows_of.get(m, [])
     st = batch.store
     members = [batch.pairs[p][1] for p in rows]
@@ -187,7 +207,11 @@ def _correct_partition_from_ops(batch, m, partition, seq_to_acc):
     if not (nr > 1 and N_t > 2):
         return out
     row_ids, ops, ops_ptr = _partition_rows(batch, m)
-    n_cols, col_slot, longest, wide = st.msa_build_ops(row_ids, ops, ops_ptr)
+    if _device_place(st, "msa_build_ops_placed"):
+        n_cols, col_slot, longest, wide, n_placed = st.msa_build_ops_placed(row_ids, ops, ops_ptr)
+        _count_placed(n_placed, wide)
+    else:
+        n_cols, col_slot, longest, wide = st.msa_build_ops(row_ids, ops, ops_ptr)
     p_row, p_col, p_ptr, p_bytes = _wide_slot_patches(members, wide, col_slot, longest)
     deg = np.ones(nr, dtype=np.int32)
     deg[0] = partition[m][3]
@@ -233,7 +257,7 @@ def _rows_intact(partition, m, batch):
 
 def _correct_all_from_ops(batch, partition_alignments, centres, seq_to_acc):
     """correct_to_consensus for ALL the given partitions (centres: sorted list) in one batched build + correct on the device
-    (isocon_msa_build_ops_batch / isocon_msa_correct_built_batch).  Returns ({accession: corrected sequence}, centres whose partition has a
+    (isocon_msa_build_ops_placed_batch / isocon_msa_correct_built_batch).  Returns ({accession: corrected sequence}, centres whose partition has a
     row with more correctable positions than the batched kernel keeps: those go through the single-partition path)."""
     st = batch.store
     first_row, idx_parts, keys, deg_parts = [0], [], [], []
@@ -267,7 +291,12 @@ def _correct_all_from_ops(batch, partition_alignments, centres, seq_to_acc):
     total = int(ops_ptr[-1])
     src = np.repeat(starts - ops_ptr[:-1].astype(np.int64), cnt) + np.arange(total, dtype=np.int64)
     ops = batch.ops[src] if total else np.zeros(0, dtype=np.uint32)
-    n_cols, slot_base, col_slot, longest, wide = st.msa_build_ops_batch(first_row, row_ids, ops, ops_ptr)
+    if _device_place(st, "msa_build_ops_placed_batch"):
+        # (what is left are the records of slots beyond 62 bases: the loop below runs over the partitions that have such a slot, normally none)
+        n_cols, slot_base, col_slot, longest, wide, n_placed = st.msa_build_ops_placed_batch(first_row, row_ids, ops, ops_ptr)
+        _count_placed(n_placed, wide)
+    else:
+        n_cols, slot_base, col_slot, longest, wide = st.msa_build_ops_batch(first_row, row_ids, ops, ops_ptr)
     p_row = p_col = p_ptr = p_bytes = None
     if len(wide):
         order = np.argsort(wide[:, 6], kind="stable")

@@ -12,7 +12,18 @@
 //   k_msa_fill         one wave per row: writes the row (the matrix is pre-filled with '-'); single-character insertions go to their
 //                      slot's column, the insertions of WIDE slots are only listed (row, slot, position in the member, length, first bases,
 //                      partition): where they sit inside the padded longest insertion is decided by get_best_solution (functions.py:635-676,
-//                      string heuristics with an alignment tie), which stays on the host and comes back as patches (k_msa_patch).
+//                      string heuristics with an alignment tie).
+// The placed builds (isocon_msa_build_ops_placed[_batch]) apply that rule on the device (msa_place_core.hpp) to every slot whose longest
+// insertion has at most PLACE_MAX_LONGEST = 62 bases -- the padded insertion then fits the 64 lanes of a wave:
+//   k_msa_wide_number  one thread per slot: numbers those slots, so that the per-slot keys scale with the wide slots and not with all slots;
+//   k_msa_slot_rep     one thread per record, two passes: the slot's representative -- the smallest of its longest insertions -- as the
+//                      atomicMin of big-endian 2-bit keys (bases 0 .. 31, then bases 32 .. 61 among the records that hold the first
+//                      minimum); the first pass also copies the records of the slots it does NOT place (longest > 62: all of them, the host
+//                      picks the representative from what it is handed) into a second list, one atomic per wave;
+//   k_msa_place        one wave per record: substring test, DP by anti-diagonals + backtrack, best offset; writes the slot's columns of the row.
+// The record list lives on the device, sized by the host from the code-3 ops (an upper bound); the result does not depend on its order,
+// duplicates are computed again.  The existing builds hand ALL records to the host, whose placements come back as patches (k_msa_patch);
+// after a placed build the patches are those of the left-over records only.
 // ops: len << 4 | code, code 0 '=', 1 'X', 2 'I' (centre base against a gap of the member), 3 'D' (member bases the centre lacks:
 // an insertion into the slot in front of the next centre base); the centre is the QUERY of its alignments (isocon_get_candidates.py:47).
 //
@@ -33,6 +44,7 @@
 // and matrix cells.
 #pragma once
 #include "common.hpp"
+#include "msa_place_core.hpp"
 
 namespace isocon {
 
@@ -144,7 +156,7 @@ __global__ __launch_bounds__(256) void k_msa_fill(DevStore S, MsaBatch B, const 
             if (lane >= d) { it += ot; is += os; }
         }
         const uint32_t t_l = t + it - (code_l == 3u ? 0u : len_l), sp_l = sp + is - (code_l == 2u ? 0u : len_l);
-        // Insertions at wide slots are only LISTED (their place inside the padded longest insertion is decided on the host): every lane files
+        // Insertions at wide slots are only LISTED (their place inside the padded longest insertion is decided by k_msa_place, or on the host): every lane files
         // its own op's record, ONE atomic per batch reserves the records (one atomic per record -- 6 10^5 on one address at C3 -- was what the
         // kernel's 3.7 ms were: same-address atomics serialise in L2).
         {
@@ -185,6 +197,149 @@ __global__ __launch_bounds__(256) void k_msa_fill(DevStore S, MsaBatch B, const 
         t += (uint32_t)__shfl((int)it, 63, 64);
         sp += (uint32_t)__shfl((int)is, 63, 64);
     }
+}
+
+// ---- the wide-slot insertions placed on the device (msa_place_core.hpp) ---------------------------------------------------------------------
+
+static constexpr uint32_t MSA_NO_WIDE = 0xffffffffu;          // wide_idx of a slot the device does not place (1 column, or longest > PLACE_MAX_LONGEST)
+
+__device__ __forceinline__ uint32_t msa_base_code(const DevStore &S, uint32_t id, uint32_t pos)
+{
+    const size_t w = ((size_t)(pos >> 6) * S.n + id) * 2;
+    const uint32_t sh = pos & 63u;
+    return (uint32_t)((S.planes[w] >> sh) & 1ull) | ((uint32_t)((S.planes[w + 1] >> sh) & 1ull) << 1);
+}
+
+// 64 bases of sequence id from position pos on, one plane; a chunk outside the store reads as 0
+__device__ __forceinline__ uint64_t msa_fetch64(const DevStore &S, uint32_t id, uint32_t plane, uint32_t pos)
+{
+    const uint32_t c = pos >> 6, sh = pos & 63u;
+    const uint64_t w0 = c < S.nchunks ? S.planes[((size_t)c * S.n + id) * 2 + plane] : 0ull;
+    if (!sh) return w0;
+    const uint64_t w1 = c + 1u < S.nchunks ? S.planes[((size_t)(c + 1u) * S.n + id) * 2 + plane] : 0ull;
+    return (w0 >> sh) | (w1 << (64u - sh));
+}
+
+// wide_idx[s] = the slot's number among the slots the device places (2 <= longest <= PLACE_MAX_LONGEST), in no particular order;
+// *n_wide_slots (zeroed by the host) = how many there are
+__global__ __launch_bounds__(256) void k_msa_wide_number(const uint32_t *__restrict__ longest, uint32_t n_slots, uint32_t *__restrict__ wide_idx, uint32_t *__restrict__ n_wide_slots)
+{
+    const int lane = threadIdx.x & 63;
+    const unsigned long long s = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
+    const bool placed = s < n_slots && longest[s] > 1u && longest[s] <= (uint32_t)PLACE_MAX_LONGEST;
+    const unsigned long long mask = __ballot(placed);
+    uint32_t base = 0;
+    if (mask != 0ull) {
+        if (lane == 0) base = atomicAdd(n_wide_slots, (uint32_t)__popcll(mask));
+        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+    }
+    if (s < n_slots) wide_idx[s] = placed ? base + (uint32_t)__popcll(mask & (((unsigned long long)1 << lane) - 1ull)) : MSA_NO_WIDE;
+}
+
+// One thread per record of `wide` (min(*wide_count, wide_cap) of them).  keys[2 x], keys[2 x + 1] (preset to PLACE_KEY_NONE) = the keys of
+// the representative of placed slot x.  PASS 1: first key; and the records of the slots that are not placed go to left (8 words each, as in
+// wide; *left_count may exceed left_cap).  PASS 2: second key, for slots with longest > 32.
+template <int PASS>
+__global__ __launch_bounds__(256) void k_msa_slot_rep(DevStore S, MsaBatch B, const uint32_t *__restrict__ row_ids, const uint32_t *__restrict__ longest_all,
+                                                       const uint32_t *__restrict__ wide_idx_all, const uint32_t *__restrict__ wide, unsigned long long wide_cap,
+                                                       const unsigned long long *__restrict__ wide_count, unsigned long long *__restrict__ keys,
+                                                       uint32_t *__restrict__ left, unsigned long long left_cap, unsigned long long *__restrict__ left_count)
+{
+    const int lane = threadIdx.x & 63;
+    const unsigned long long n = *wide_count < wide_cap ? *wide_count : wide_cap;
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
+    const bool have = i < n;
+    const uint32_t *e = wide + 8 * (have ? i : 0ull);
+    uint32_t idx = MSA_NO_WIDE, lg = 0, len = 0;
+    unsigned long long codes = 0;
+    if (have) {
+        const uint32_t sb = B.slot_base[e[6]];
+        idx = wide_idx_all[sb + e[1]];
+        lg = longest_all[sb + e[1]];
+        len = e[3];
+        codes = (unsigned long long)e[4] | ((unsigned long long)e[5] << 32);
+    }
+    if (PASS == 1) {
+        const bool over = have && idx == MSA_NO_WIDE;
+        const unsigned long long mask = __ballot(over);
+        if (mask != 0ull) {
+            unsigned long long at0 = 0;
+            if (lane == 0) at0 = atomicAdd(left_count, (unsigned long long)__popcll(mask));
+            at0 = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(at0 >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)at0);
+            const unsigned long long at = at0 + (unsigned long long)__popcll(mask & (((unsigned long long)1 << lane) - 1ull));
+            if (over && at < left_cap)
+                for (int k = 0; k < 8; ++k) left[8 * at + k] = e[k];
+        }
+        if (have && idx != MSA_NO_WIDE && len == lg) atomicMin(keys + 2 * (size_t)idx, (unsigned long long)place_key_of_codes(codes));
+    } else {
+        if (have && idx != MSA_NO_WIDE && len == lg && lg > 32u && place_key_of_codes(codes) == keys[2 * (size_t)idx]) {
+            const uint32_t id = row_ids[e[0]], pos = e[2] + 32u;
+            atomicMin(keys + 2 * (size_t)idx + 1, (unsigned long long)place_key_of_planes(msa_fetch64(S, id, 0, pos), msa_fetch64(S, id, 1, pos), (int)(len - 32u)));
+        }
+    }
+}
+
+// One wave per record, four per workgroup: the record's insertion q (its first 32 bases from the record, the rest from the store's planes)
+// inside '-' + its slot's representative + '-' (from the slot's keys), written into the L = longest + 2 columns of the slot in the record's row.
+// Everything that decides a branch is wave-uniform: the strings are words the whole wave shares (PlaceStr), each step's outcome a ballot or a
+// wave maximum.  LDS: the DP bytes, PLACE_DP_BYTES per wave.
+__global__ __launch_bounds__(256) void k_msa_place(DevStore S, MsaBatch B, const uint32_t *__restrict__ row_ids, const uint32_t *__restrict__ longest_all,
+                                                    const uint32_t *__restrict__ col_slot_all, const uint32_t *__restrict__ wide_idx_all,
+                                                    const unsigned long long *__restrict__ keys, const uint32_t *__restrict__ wide, unsigned long long wide_cap,
+                                                    const unsigned long long *__restrict__ wide_count, uint8_t *__restrict__ M_all)
+{
+    __shared__ uint8_t s_D[4][PLACE_DP_BYTES];
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned long long n = *wide_count < wide_cap ? *wide_count : wide_cap;
+    const unsigned long long i = (unsigned long long)blockIdx.x * 4ull + wave;
+    if (i >= n) return;
+    const uint32_t *e = wide + 8 * i;
+    const uint32_t r = e[0], t = e[1], sp = e[2], p = e[6];
+    const int m = (int)e[3];
+    const unsigned long long codes = (unsigned long long)e[4] | ((unsigned long long)e[5] << 32);
+    const uint32_t sb = B.slot_base[p], idx = wide_idx_all[sb + t];
+    if (idx == MSA_NO_WIDE) return;          // (a slot left to the host)
+    const int lg = (int)longest_all[sb + t], L = lg + 2;
+    if (m < 1 || m > lg || lg > PLACE_MAX_LONGEST) return;          // (cannot be: longest is the maximum over these very records)
+    const unsigned long long k1 = keys[2 * (size_t)idx], k2 = keys[2 * (size_t)idx + 1];
+    const uint32_t rc = lane < lg ? place_key_code(k1, k2, lane) : 0u;
+    const PlaceStr mx = place_padded(__ballot((rc & 1u) != 0u), __ballot((rc & 2u) != 0u), lg);
+    uint32_t qc = 0;
+    if (lane < m) qc = lane < 32 ? (uint32_t)((codes >> (2 * lane)) & 3ull) : msa_base_code(S, row_ids[r], sp + (uint32_t)lane);
+    PlaceStr q, o;
+    q.v = place_low(m);
+    q.b0 = __ballot((qc & 1u) != 0u);
+    q.b1 = __ballot((qc & 2u) != 0u);
+    const unsigned long long found = __ballot(lane <= L - m && place_eq(mx, q, lane) == q.v);
+    if (found != 0ull) o = place_at(q, __builtin_ctzll(found));          // 1. substring: the first occurrence
+    else {
+        uint8_t *D = s_D[wave];
+        uint32_t prev = 0, prev2 = 0, cur = 0;          // this lane's column j = lane + 1 on the two previous anti-diagonals
+        const int j = lane + 1;
+        for (int d = 2; d <= L + m; ++d) {
+            const uint32_t left_in = (uint32_t)__shfl_up((int)prev, 1, 64), diag_in = (uint32_t)__shfl_up((int)prev2, 1, 64);
+            const int ii = d - j;
+            if (j <= m && ii >= 1 && ii <= L) {
+                const uint32_t up = ii == 1 ? (uint32_t)j : prev;
+                const uint32_t left = lane == 0 ? (uint32_t)ii : left_in;
+                const uint32_t diag = lane == 0 ? (uint32_t)(ii - 1) : ii == 1 ? (uint32_t)(j - 1) : diag_in;
+                cur = place_dp_value(up, left, diag, mx, q, ii, j);
+                D[place_dp_index(ii, j)] = (uint8_t)cur;
+            }
+            prev2 = prev;
+            prev = cur;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");          // (the backtrack reads what other lanes of the wave wrote)
+        __builtin_amdgcn_wave_barrier();
+        if (!place_thread(D, L, m, q, o)) {          // 2. threading, else 3. the offset with the most matches
+            uint32_t key = lane <= L - m ? place_offset_key(mx, q, lane) : 0u;
+            for (int s = 32; s > 0; s >>= 1) { const uint32_t other = (uint32_t)__shfl_xor((int)key, s, 64); key = other > key ? other : key; }
+            o = place_at(q, place_offset_of_key((uint32_t)__builtin_amdgcn_readfirstlane((int)key)));
+        }
+    }
+    uint8_t *row = M_all + B.m_off[p] + (size_t)(r - B.first_row[p]) * B.ncols[p] + col_slot_all[sb + t];
+    if (lane < L) row[lane] = place_char(o, lane);
 }
 
 // patches: bytes[ptr[i] .. ptr[i + 1]) go to row patch_row[i] (of the concatenation) from column patch_col[i] of its matrix on (one wave per patch)

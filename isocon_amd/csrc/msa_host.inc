@@ -28,10 +28,21 @@ MsaBatch msa_batch_desc(ScratchPool *pl, uint32_t n_parts, uint32_t n_rows)
     return B;
 }
 
+// what a placed build hands back: the records of the slots it left to the host, and how many it placed
+struct MsaPlaced {
+    uint32_t *out_left;
+    uint64_t left_cap, *n_left, *n_placed;
+};
+
 // The matrices of n_parts partitions from the ops of their rows (the arguments of isocon_msa_build_ops_batch), left in SLOT_MSA_IN and
 // described by the store's pool->msa, tagged `by`.  A refused build leaves no build.
+// placed != nullptr (isocon_msa_build_ops_placed[_batch]): the record list stays on the device -- sized here from the code-3 ops, an upper
+// bound, so it never overflows; out_wide / wide_cap / n_wide are not used -- and the insertions of the wide slots are placed there
+// (k_msa_slot_rep, k_msa_place); only the records of slots beyond PLACE_MAX_LONGEST come back.  Between fill and place the host waits for
+// nothing: the number of wide slots comes with the one read after the layout, the record counts with the one read at the end.
 int msa_build(isocon_store *s, MsaBuilt::By by, uint32_t n_parts, const uint32_t *first_row, const uint32_t *row_ids, const uint32_t *ops, const uint64_t *ops_ptr,
-              uint32_t *out_n_cols, uint32_t *out_col_slot, uint32_t *out_longest, uint32_t *out_wide, uint64_t wide_cap, uint64_t *n_wide, float *kernel_ms)
+              uint32_t *out_n_cols, uint32_t *out_col_slot, uint32_t *out_longest, uint32_t *out_wide, uint64_t wide_cap, uint64_t *n_wide, float *kernel_ms,
+              const MsaPlaced *placed = nullptr)
 {
     if (kernel_ms) *kernel_ms = 0.f;
     if (!s->acgt) { g_last_error = "the consensus correction needs a store over the alphabet ACGT"; return ISOCON_E_ALPHABET; }
@@ -56,11 +67,15 @@ int msa_build(isocon_store *s, MsaBuilt::By by, uint32_t n_parts, const uint32_t
     if (ops_ptr[0] != 0) { g_last_error = centre_with_ops; return ISOCON_E_ARG; }
     if (n_ops && !ops) return ISOCON_E_ARG;
     const uint32_t n_slots = slot_base[n_parts];
+    if (placed) {
+        wide_cap = 0;
+        for (uint64_t k = 0; k < n_ops; ++k) wide_cap += (ops[k] & 15u) == 3u;
+    }
     ScratchPool *pl = &s->pool;
     MsaBuilt &H = pl->msa;
     H = MsaBuilt();
     DevBuf d_longest(pl, SLOT_MSA_LONGEST), d_width(pl, SLOT_MSA_WIDTH), d_cslot(pl, SLOT_MSA_CSLOT), d_tot(pl, SLOT_MSA_LTOT), d_wide(pl, SLOT_MSA_WIDE), d_M(pl, SLOT_MSA_IN),
-        d_ncols(pl, SLOT_MSA_NCOLS);
+        d_ncols(pl, SLOT_MSA_NCOLS), d_widx(pl, SLOT_MSA_WIDX), d_keys(pl, SLOT_MSA_KEYS), d_left(pl, SLOT_MSA_LEFT);
     int rc;
     if ((rc = msa_upload(pl, SLOT_MSA_ROWS, row_ids, (size_t)n_rows * 4)) || (rc = msa_upload(pl, SLOT_MSA_OPS, ops, (size_t)n_ops * 4)) ||
         (rc = msa_upload(pl, SLOT_MSA_OPTR, ops_ptr, (size_t)(n_rows + 1) * 8)) || (rc = msa_upload(pl, SLOT_MSA_PART, part_of_row.data(), (size_t)n_rows * 4)) ||
@@ -69,16 +84,18 @@ int msa_build(isocon_store *s, MsaBuilt::By by, uint32_t n_parts, const uint32_t
         (rc = d_width.alloc((size_t)n_slots * 4)) || (rc = d_cslot.alloc((size_t)n_slots * 4)) || (rc = d_tot.alloc(32)) ||
         (rc = d_wide.alloc((size_t)std::max<uint64_t>(wide_cap, 1) * 32)) || (rc = d_ncols.alloc((size_t)n_parts * 4)))
         return rc;
+    if (placed && ((rc = d_widx.alloc((size_t)n_slots * 4)) || (rc = d_left.alloc((size_t)std::max<uint64_t>(placed->left_cap, 1) * 32)))) return rc;
     const uint32_t *d_rows = msa_slot<uint32_t>(pl, SLOT_MSA_ROWS), *d_ops = msa_slot<uint32_t>(pl, SLOT_MSA_OPS);
     const unsigned long long *d_optr = msa_slot<unsigned long long>(pl, SLOT_MSA_OPTR);
     ISO_HIP_CHECK(hipMemsetAsync(d_longest.p, 0, (size_t)n_slots * 4, 0));
     ISO_HIP_CHECK(hipMemsetAsync(d_tot.p, 0, 32, 0));
-    uint32_t *tot = d_tot.as<uint32_t>();          // [2] bad flag, [4..5] wide records (64 bit)
+    uint32_t *tot = d_tot.as<uint32_t>();          // [0] wide slots placed on the device, [2] bad flag, [4..5] wide records, [6..7] left-over records (64 bit)
     MsaBatch B = msa_batch_desc(pl, n_parts, n_rows);          // (m_off and col_base follow the layout)
     EventTimer tm;
     tm.start();
     hipLaunchKernelGGL(k_msa_ops_scan, dim3((n_rows + 255) / 256), dim3(256), 0, 0, s->dev, B, d_rows, d_ops, d_optr, d_longest.as<uint32_t>(), tot + 2);
     hipLaunchKernelGGL(k_msa_layout, dim3(n_parts), dim3(1024), 0, 0, B, d_longest.as<uint32_t>(), d_width.as<uint32_t>(), d_cslot.as<uint32_t>(), d_ncols.as<uint32_t>());
+    if (placed) hipLaunchKernelGGL(k_msa_wide_number, dim3((n_slots + 255) / 256), dim3(256), 0, 0, d_longest.as<uint32_t>(), n_slots, d_widx.as<uint32_t>(), tot);
     ISO_HIP_CHECK(hipGetLastError());
     tm.stop();
     uint32_t h_tot[4];
@@ -100,26 +117,51 @@ int msa_build(isocon_store *s, MsaBuilt::By by, uint32_t n_parts, const uint32_t
         (rc = msa_upload(pl, SLOT_MSA_CBASE, H.col_base.data(), (size_t)(n_parts + 1) * 4)))
         return rc;
     ISO_HIP_CHECK(hipMemsetAsync(d_M.p, '-', cells, 0));
+    const uint32_t n_wide_slots = placed ? h_tot[0] : 0u;
+    if (placed) {
+        if ((rc = d_keys.alloc((size_t)std::max<uint32_t>(n_wide_slots, 1) * 16))) return rc;
+        ISO_HIP_CHECK(hipMemsetAsync(d_keys.p, 0xff, (size_t)n_wide_slots * 16, 0));          // PLACE_KEY_NONE
+    }
     B = msa_batch_desc(pl, n_parts, n_rows);
     tm.start();
     hipLaunchKernelGGL(k_msa_fill, dim3((n_rows + 3) / 4), dim3(256), 0, 0, s->dev, B, d_rows, d_ops, d_optr, d_longest.as<uint32_t>(),
                        d_width.as<uint32_t>(), d_cslot.as<uint32_t>(), d_M.as<uint8_t>(), d_wide.as<uint32_t>(), (unsigned long long)wide_cap,
                        reinterpret_cast<unsigned long long *>(tot + 4));
+    if (placed && wide_cap && n_wide_slots) {          // (grids by the upper bound: a thread or wave beyond the records that were listed ends at once)
+        unsigned long long *cnt_w = reinterpret_cast<unsigned long long *>(tot + 4), *cnt_l = reinterpret_cast<unsigned long long *>(tot + 6);
+        const unsigned long long lcap = placed->left_cap;
+        hipLaunchKernelGGL(k_msa_slot_rep<1>, dim3((unsigned)((wide_cap + 255) / 256)), dim3(256), 0, 0, s->dev, B, d_rows, d_longest.as<uint32_t>(), d_widx.as<uint32_t>(),
+                           d_wide.as<uint32_t>(), (unsigned long long)wide_cap, cnt_w, d_keys.as<unsigned long long>(), d_left.as<uint32_t>(), lcap, cnt_l);
+        hipLaunchKernelGGL(k_msa_slot_rep<2>, dim3((unsigned)((wide_cap + 255) / 256)), dim3(256), 0, 0, s->dev, B, d_rows, d_longest.as<uint32_t>(), d_widx.as<uint32_t>(),
+                           d_wide.as<uint32_t>(), (unsigned long long)wide_cap, cnt_w, d_keys.as<unsigned long long>(), d_left.as<uint32_t>(), lcap, cnt_l);
+        hipLaunchKernelGGL(k_msa_place, dim3((unsigned)((wide_cap + 3) / 4)), dim3(256), 0, 0, s->dev, B, d_rows, d_longest.as<uint32_t>(), d_cslot.as<uint32_t>(),
+                           d_widx.as<uint32_t>(), d_keys.as<unsigned long long>(), d_wide.as<uint32_t>(), (unsigned long long)wide_cap, cnt_w, d_M.as<uint8_t>());
+    }
     ISO_HIP_CHECK(hipGetLastError());
     tm.stop();
     if (kernel_ms) *kernel_ms = tm.total;
-    unsigned long long cnt = 0;
-    ISO_HIP_CHECK(hipMemcpy(&cnt, tot + 4, 8, hipMemcpyDeviceToHost));
-    *n_wide = cnt;
-    if (cnt > wide_cap) return ISOCON_E_CAPACITY;          // (call again with room for *n_wide records)
-    if (cnt) ISO_HIP_CHECK(copy_d2h(out_wide, d_wide.p, (size_t)cnt * 32));
+    unsigned long long cnt[2] = {0, 0};          // records listed; of them left to the host
+    ISO_HIP_CHECK(hipMemcpy(cnt, tot + 4, 16, hipMemcpyDeviceToHost));
+    bool too_small = false;
+    if (placed) {
+        if (cnt[0] > wide_cap) { g_last_error = "more wide-slot records than code-3 ops"; return ISOCON_E_ARG; }
+        if (!n_wide_slots) cnt[1] = cnt[0];          // (no slot for the device: every record is left; listed below)
+        *placed->n_left = cnt[1];
+        *placed->n_placed = cnt[0] - cnt[1];
+        too_small = cnt[1] > placed->left_cap;          // (the matrix is built all the same: the caller calls again for the list)
+        if (!too_small && cnt[1]) ISO_HIP_CHECK(copy_d2h(placed->out_left, n_wide_slots ? d_left.p : d_wide.p, (size_t)cnt[1] * 32));
+    } else {
+        *n_wide = cnt[0];
+        if (cnt[0] > wide_cap) return ISOCON_E_CAPACITY;          // (call again with room for *n_wide records)
+        if (cnt[0]) ISO_HIP_CHECK(copy_d2h(out_wide, d_wide.p, (size_t)cnt[0] * 32));
+    }
     if (out_col_slot) ISO_HIP_CHECK(copy_d2h(out_col_slot, d_cslot.p, (size_t)n_slots * 4));
     if (out_longest) ISO_HIP_CHECK(copy_d2h(out_longest, d_longest.p, (size_t)n_slots * 4));
     H.by = by;
     H.serial = s->serial;
     H.n_parts = n_parts;
     H.n_rows = n_rows;
-    return ISOCON_OK;
+    return too_small ? ISOCON_E_CAPACITY : ISOCON_OK;
 }
 
 // nullptr, or what is wrong with the first patch that does not lie inside its row's matrix
@@ -272,6 +314,16 @@ extern "C" int isocon_msa_build_ops(isocon_store *s, uint32_t n_rows, const uint
     return msa_build(s, MsaBuilt::SINGLE, 1, first_row, row_ids, ops, ops_ptr, out_n_cols, out_col_slot, out_longest, out_wide, wide_cap, n_wide, kernel_ms);
 }
 
+extern "C" int isocon_msa_build_ops_placed(isocon_store *s, uint32_t n_rows, const uint32_t *row_ids, const uint32_t *ops, const uint64_t *ops_ptr,
+                                           uint32_t *out_n_cols, uint32_t *out_col_slot, uint32_t *out_longest, uint32_t *out_left, uint64_t left_cap,
+                                           uint64_t *n_left, uint64_t *n_placed, float *kernel_ms)
+{
+    if (!s || !row_ids || !ops_ptr || !out_n_cols || !n_left || !n_placed || n_rows == 0 || (left_cap && !out_left)) return ISOCON_E_ARG;
+    const uint32_t first_row[2] = {0, n_rows};
+    const MsaPlaced placed = {out_left, left_cap, n_left, n_placed};
+    return msa_build(s, MsaBuilt::SINGLE, 1, first_row, row_ids, ops, ops_ptr, out_n_cols, out_col_slot, out_longest, nullptr, 0, nullptr, kernel_ms, &placed);
+}
+
 extern "C" int isocon_msa_correct_built(isocon_store *s, uint32_t n_rows, uint32_t n_cols, const uint32_t *patch_row, const uint32_t *patch_col,
                                         const uint32_t *patch_ptr, const uint8_t *patch_bytes, uint32_t n_patches, const int32_t *degree,
                                         uint8_t *out_packed, uint64_t packed_cap, uint64_t *out_offsets, int32_t *out_n_cand,
@@ -308,6 +360,15 @@ extern "C" int isocon_msa_build_ops_batch(isocon_store *s, uint32_t n_parts, con
 {
     if (!s || !first_row || !row_ids || !ops_ptr || !out_n_cols || !n_wide || n_parts == 0 || (wide_cap && !out_wide)) return ISOCON_E_ARG;
     return msa_build(s, MsaBuilt::BATCH, n_parts, first_row, row_ids, ops, ops_ptr, out_n_cols, out_col_slot, out_longest, out_wide, wide_cap, n_wide, kernel_ms);
+}
+
+extern "C" int isocon_msa_build_ops_placed_batch(isocon_store *s, uint32_t n_parts, const uint32_t *first_row, const uint32_t *row_ids, const uint32_t *ops,
+                                                 const uint64_t *ops_ptr, uint32_t *out_n_cols, uint32_t *out_col_slot, uint32_t *out_longest, uint32_t *out_left,
+                                                 uint64_t left_cap, uint64_t *n_left, uint64_t *n_placed, float *kernel_ms)
+{
+    if (!s || !first_row || !row_ids || !ops_ptr || !out_n_cols || !n_left || !n_placed || n_parts == 0 || (left_cap && !out_left)) return ISOCON_E_ARG;
+    const MsaPlaced placed = {out_left, left_cap, n_left, n_placed};
+    return msa_build(s, MsaBuilt::BATCH, n_parts, first_row, row_ids, ops, ops_ptr, out_n_cols, out_col_slot, out_longest, nullptr, 0, nullptr, kernel_ms, &placed);
 }
 
 // a row with more than MSA_BATCH_CAND correctable positions keeps n_cand = -1: the caller corrects its partition through the single-partition entries

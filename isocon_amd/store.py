@@ -521,18 +521,73 @@ class SeqStore(object):
         # room for the wide-slot records: a too-small buffer means building everything again (two 3.7 ms fill launches per correction step at
         # C3 with the old fixed 2^17); what the previous call of this store needed is the best guess for the next one
         cap = max(1 << 17, 8 * len(row_ids), int(1.25 * getattr(self, "_msa_wide_seen", 0)) + 16)
-        n_wide = ctypes.c_uint64(0)
+        n_wide, ms = ctypes.c_uint64(0), ctypes.c_float(0.0)
         while True:
             wide = np.empty((cap, 8), dtype=np.uint32)
             rc = self._L.isocon_msa_build_ops_batch(self._h, n_parts, _ptr(first_row, _lib.u32p), _ptr(row_ids, _lib.u32p), _ptr(ops if len(ops) else None, _lib.u32p),
                                                     _ptr(ops_ptr, _lib.u64p), _ptr(n_cols, _lib.u32p), _ptr(col_slot, _lib.u32p), _ptr(longest, _lib.u32p),
-                                                    _ptr(wide, _lib.u32p), cap, ctypes.byref(n_wide), None)
+                                                    _ptr(wide, _lib.u32p), cap, ctypes.byref(n_wide), ctypes.byref(ms))
             if rc == _lib.ISOCON_E_CAPACITY:
                 cap = int(n_wide.value) + 16
                 continue
             _lib.check(rc, "isocon_msa_build_ops_batch")
             self._msa_wide_seen = int(n_wide.value)
+            self.msa_build_ms = float(ms.value)          # HIP-event time of the build's kernels (timing scripts)
             return n_cols, slot_base, col_slot, longest, wide[:int(n_wide.value)]
+
+    def msa_build_ops_placed(self, row_ids, ops, ops_ptr):
+        """msa_build_ops with the insertions of the wide slots placed on the device (isocon_msa_build_ops_placed) -> (n_cols, col_slot, longest,
+        left uint32[k, 8]: the records of the slots whose longest insertion has more than 62 bases -- normally none -- for the caller to
+        place, n_placed: records placed on the device)."""
+        row_ids = np.ascontiguousarray(row_ids, dtype=np.uint32)
+        ops = np.ascontiguousarray(ops, dtype=np.uint32)
+        ops_ptr = np.ascontiguousarray(ops_ptr, dtype=np.uint64)
+        Lm = int(self.lens[int(row_ids[0])])
+        n_cols = ctypes.c_uint32(0)
+        col_slot = np.zeros(Lm + 1, dtype=np.uint32)
+        longest = np.zeros(Lm + 1, dtype=np.uint32)
+        cap = 1024
+        n_left, n_placed = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        while True:
+            left = np.empty((cap, 8), dtype=np.uint32)
+            rc = self._L.isocon_msa_build_ops_placed(self._h, len(row_ids), _ptr(row_ids, _lib.u32p), _ptr(ops if len(ops) else None, _lib.u32p),
+                                                     _ptr(ops_ptr, _lib.u64p), ctypes.byref(n_cols), _ptr(col_slot, _lib.u32p), _ptr(longest, _lib.u32p),
+                                                     _ptr(left, _lib.u32p), cap, ctypes.byref(n_left), ctypes.byref(n_placed), None)
+            if rc == _lib.ISOCON_E_CAPACITY:
+                cap = int(n_left.value) + 16
+                continue
+            _lib.check(rc, "isocon_msa_build_ops_placed")
+            return int(n_cols.value), col_slot, longest, left[:int(n_left.value)], int(n_placed.value)
+
+    def msa_build_ops_placed_batch(self, first_row, row_ids, ops, ops_ptr):
+        """msa_build_ops_batch with the insertions of the wide slots placed on the device (isocon_msa_build_ops_placed_batch) -> (n_cols,
+        slot_base, col_slot, longest, left uint32[k, 8]: the records of the slots beyond 62 bases, n_placed)."""
+        first_row = np.ascontiguousarray(first_row, dtype=np.uint32)
+        row_ids = np.ascontiguousarray(row_ids, dtype=np.uint32)
+        ops = np.ascontiguousarray(ops, dtype=np.uint32)
+        ops_ptr = np.ascontiguousarray(ops_ptr, dtype=np.uint64)
+        n_parts = len(first_row) - 1
+        Lm = self.lens[row_ids[first_row[:-1]]].astype(np.int64)
+        slot_base = np.zeros(n_parts + 1, dtype=np.int64)
+        np.cumsum(Lm + 1, out=slot_base[1:])
+        n_cols = np.zeros(n_parts, dtype=np.uint32)
+        col_slot = np.zeros(int(slot_base[-1]), dtype=np.uint32)
+        longest = np.zeros(int(slot_base[-1]), dtype=np.uint32)
+        cap = 4096
+        n_left, n_placed = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        ms = ctypes.c_float(0.0)
+        while True:
+            left = np.empty((cap, 8), dtype=np.uint32)
+            rc = self._L.isocon_msa_build_ops_placed_batch(self._h, n_parts, _ptr(first_row, _lib.u32p), _ptr(row_ids, _lib.u32p),
+                                                           _ptr(ops if len(ops) else None, _lib.u32p), _ptr(ops_ptr, _lib.u64p), _ptr(n_cols, _lib.u32p),
+                                                           _ptr(col_slot, _lib.u32p), _ptr(longest, _lib.u32p), _ptr(left, _lib.u32p), cap,
+                                                           ctypes.byref(n_left), ctypes.byref(n_placed), ctypes.byref(ms))
+            if rc == _lib.ISOCON_E_CAPACITY:
+                cap = int(n_left.value) + 16
+                continue
+            _lib.check(rc, "isocon_msa_build_ops_placed_batch")
+            self.msa_build_ms = float(ms.value)
+            return n_cols, slot_base, col_slot, longest, left[:int(n_left.value)], int(n_placed.value)
 
     def msa_correct_built_batch(self, n_parts, n_rows, degree, packed_cap, patch_row=None, patch_col=None, patch_ptr=None, patch_bytes=None):
         """Patches + correction of the batch built by msa_build_ops_batch -> (packed uint8[], offsets int64[n_rows + 1], n_cand int32[n_rows])."""
