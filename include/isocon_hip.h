@@ -564,6 +564,31 @@ int isocon_hw_path_pairs(isocon_store *s, const uint32_t *q, const uint32_t *t, 
                          uint64_t *needed, float *kernel_ms);
 
 /*
+ * Every best location of an infix pair: the `locations` of edlib.align(q, t, mode="HW", task="path", k).  With D the infix matrix (zero
+ * top row) of query q[p] (length P) and target t[p], h = min over columns j >= 1 of D[P][j]: out_ed[p] = h if h <= k[p], else -1.  A hit
+ * owns the locations out_loc_ptr[p] .. out_loc_ptr[p + 1]), two int32 (start, end) each in out_locs: one per 0-based column end = j - 1 with
+ * D[P][j] == h, in ascending order of the end, each with the smallest start s with ed(q, t[s..end]) == h.  The first location of a pair
+ * is the (start, end) isocon_hw_pairs returns for it; a miss (out_ed[p] = -1: above k[p], an empty sequence, len(t) - len(q) < -k[p]) owns
+ * none.  Argument checks, alphabet rule and band limit are those of isocon_hw_pairs: a store of more than four symbols ISOCON_E_ALPHABET, a
+ * pair whose band max(len(t) - len(q), 0) + 2 k[p] + 1 exceeds 512 diagonals ISOCON_E_UNSUPPORTED for the call.  ISOCON_E_CAPACITY +
+ * *needed when the locations exceed cap (out_ed and out_loc_ptr are valid then).  At most 2^32 - 16 locations per call.
+ * All stages run on the device: the distance and first end of every pair by the kernels of isocon_hw_pairs, the ends by the same
+ * recurrence on the hits with threshold h (run twice: count, then fill), the start of every (pair, end) by the start pass of
+ * isocon_hw_pairs on diagonals [-h, h].  *kernel_ms sums them.
+ */
+int isocon_hw_locations(isocon_store *s, const uint32_t *q, const uint32_t *t, const int32_t *k, uint64_t n_pairs,
+                        int32_t *out_ed /* n_pairs */, uint64_t *out_loc_ptr /* n_pairs + 1 */, int32_t *out_locs /* cap x 2 */,
+                        uint64_t cap, uint64_t *needed, float *kernel_ms);
+
+/*
+ * What the calling thread's last isocon_hw_locations call did (no counterpart in the reference; tests and timing scripts): out[0] pairs,
+ * out[1] hits, out[2] locations, out[3] stages whose tiles were cut on the host (a run of 64 pairs of one query with a common window
+ * above 512 diagonals), then the tiles per class of 1, 2, 4, 8 window words of the distance stage out[4..7], of an ends run out[8..11]
+ * and of the start stage out[12..15].  Writes min(cap, 16) values and returns that number.
+ */
+int isocon_hw_locations_last_stats(double *out, int32_t cap);
+
+/*
  * How the calling thread's last isocon_ed_path_pairs / isocon_hw_path_pairs call traced its hits (no counterpart in the reference).
  * out[0] hits traced; out[1..3] hits of the banded classes of 1, 2 and 4 window words (64, 128, 256 diagonals); out[4] hits of the
  * un-banded kernel; out[5] / out[6] bytes of trace banded / un-banded; out[7] / out[8] launches banded / un-banded; out[9] / out[10]

@@ -21,10 +21,12 @@
 
 namespace isocon {
 
-enum { HW_LOCATE = 0, HW_START = 1, HW_TRACE = 2, HW_TRACE_CK = 3 };
+enum { HW_LOCATE = 0, HW_START = 1, HW_TRACE = 2, HW_TRACE_CK = 3, HW_ENDS = 4 };
 // HW_TRACE_CK: the TRACE pass that keeps only CHECKPOINTS -- the band state (VP, VN) after every HW_SEG-th column -- instead of every
 // column's VP / HP: the walk then goes segment by segment from the end, each segment's columns recomputed from its checkpoint
 // (hw_trace_segment) into a small buffer (LDS on the device) and walked there (hw_walk_segment).  1 byte per column and word instead of 16.
+// HW_ENDS: the LOCATE recurrence run again on a hit with its distance as the threshold (ln.k = ln.h = h): every column whose last-row value
+// equals h goes to the sink, in ascending order -- all the end positions edlib reports for the pair, not only the first.
 static constexpr int HW_SEG = 8;
 static constexpr int32_t HWB_INF = 1 << 28;
 
@@ -108,11 +110,14 @@ ISO_HD uint32_t hw_bit(const uint64_t (&V)[W], int32_t r)
 // caller hands a forward or a reversed stream); text(jb, wl, wh): the lane's target bits of columns jb + 1 .. jb + 32;
 // any_live(live): does any lane of the wave still need columns (device: a ballot; emulator: the lane itself);
 // sink(j, word, vp_new, hp): TRACE; sink(j / HW_SEG, word, vp_new, vn_new) after every column j that is a multiple of HW_SEG: TRACE_CK
-// (there T.jx = the smallest ncols of the tile's lanes: the blocks before it take the unrolled path).
+// (there T.jx = the smallest ncols of the tile's lanes: the blocks before it take the unrolled path); sink(end, 0, 0, 0) for every
+// 0-based column `end` whose last-row value equals ln.h: ENDS.  ENDS abandons a lane by LOCATE's rule with ln.k = h, which stays sound
+// for the later ends: while a later occurrence can still start at or behind the current column the window's top row is a virtual row
+// (D = 0), so the bound is <= 0; afterwards every alignment of cost <= h that ends in a later column crosses this column inside the band.
 template <int W, int MODE, class PLo, class PHi, class Text, class AnyLive, class Sink>
 ISO_HD void hw_run(const HwTile &T, HwLane &ln, PLo plo, PHi phi, Text text, AnyLive any_live, Sink sink)
 {
-    constexpr bool ZT = MODE == HW_LOCATE;
+    constexpr bool ZT = MODE == HW_LOCATE || MODE == HW_ENDS;
     const int32_t nv = -T.a0;
     BandLane<W> L;
     uint64_t NL[W], NH[W], VM[W], FL = 0, FH = 0;
@@ -182,6 +187,10 @@ ISO_HD void hw_run(const HwTile &T, HwLane &ln, PLo plo, PHi phi, Text text, Any
                         const int32_t v = hw_row_value<W>(L, top, b);
                         if (v < h) { h = v; end = j - 1; }
                     }
+                } else if (MODE == HW_ENDS) {
+                    if (live && j >= T.P - ln.k && j <= ln.ncols && b >= 0 && b < 64 * W) {
+                        if (hw_row_value<W>(L, top, b) == ln.h) sink(j - 1, 0, 0, 0);
+                    }
                 } else if (MODE == HW_START) {
                     if (j >= T.jx && j <= ln.ncols && b >= 0 && b < 64 * W) {
                         if (hw_row_value<W>(L, top, b) == ln.h) pl = j;
@@ -207,7 +216,7 @@ ISO_HD void hw_run(const HwTile &T, HwLane &ln, PLo plo, PHi phi, Text text, Any
                 }
             }
         }
-        if (MODE == HW_LOCATE) {
+        if (ZT) {
             if (live) {
                 const int32_t cols = jb + cnt;
                 if (cols >= ln.ncols) live = false;

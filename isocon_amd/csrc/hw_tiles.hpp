@@ -40,7 +40,8 @@ __device__ __forceinline__ uint32_t hwt_wave_add(uint32_t *__restrict__ counters
 }
 
 // STAGE 0 (LOCATE): every pair that needs a kernel gets key = 4 query + class of its own band; the others (distance > k by the lengths
-// alone, an empty sequence) none; out5 / he get their "no hit" rows.  STAGE 1 (START + TRACE): the hits of he.
+// alone, an empty sequence) none; out5 / he get their "no hit" rows.  STAGE 1 (START + TRACE): the hits of he.  STAGE 2 (ENDS of
+// isocon_hw_locations): k[p] = the pair's distance or -1, the hits keyed by the LOCATE band of that distance; he / out5 are not touched.
 template <int STAGE>
 __global__ __launch_bounds__(256) void k_hwt_keys(DevStore S, const uint32_t *__restrict__ q, const uint32_t *__restrict__ t, const int32_t *__restrict__ k,
                                                    unsigned long long n_pairs, int32_t *__restrict__ he, int32_t *__restrict__ out5, uint32_t *__restrict__ key,
@@ -68,6 +69,13 @@ __global__ __launch_bounds__(256) void k_hwt_keys(DevStore S, const uint32_t *__
             he[p * 2] = -1; he[p * 2 + 1] = -1;
             int32_t *o = out5 + p * 5;
             o[0] = -1; o[1] = -1; o[2] = -1; o[3] = 0; o[4] = 0;
+        } else if (STAGE == 2) {
+            if (kv < -1) atomicOr(&ctr->flags, (uint32_t)HWT_ERR_STATUS);
+            else if (kv >= 0) {
+                const int w = hwt_words(hw_locate_rows(S.lens[tt] - S.lens[qq], kv));          // (h <= k: no wider than the pair's LOCATE band)
+                if (!w) atomicOr(&ctr->flags, (uint32_t)HWT_ERR_BAND);
+                else kk = qq * 4u + hwt_class(w);
+            }
         } else {
             const int32_t h = he[p * 2];
             if (h < -1) atomicOr(&ctr->flags, (uint32_t)HWT_ERR_STATUS);
@@ -110,7 +118,7 @@ __global__ __launch_bounds__(256) void k_hwt_classes(DevStore S, const uint32_t 
     const int32_t kv = has ? k[pair] : 0;
     const int32_t delta = has ? S.lens[t[pair]] - P : -(1 << 30);
     const int32_t dmax = wave_max_i32(delta), kmax = wave_max_i32(kv);
-    const int w = hwt_words(STAGE == 0 ? hw_locate_rows(dmax, kmax) : 2 * kmax + 1);
+    const int w = hwt_words(STAGE != 1 ? hw_locate_rows(dmax, kmax) : 2 * kmax + 1);
     if (lane == 0) {
         if (!w) atomicOr(&ctr->flags, (uint32_t)HWT_ERR_TILE_BAND);
         else {

@@ -111,6 +111,8 @@ TRACEBACK_STATS = {"device": 0, "host": 0}
 # the calls of edlib_traceback_infix (isocon_hw_path_pairs; it has the device route alone).  A dict of its own: TRACEBACK_STATS holds
 # exactly the two routes of edlib_traceback, and its callers compare it whole
 TRACEBACK_INFIX_STATS = {"device": 0}
+# the calls of edlib_traceback_infix_all (isocon_hw_locations + isocon_hw_path_pairs; the device route alone)
+TRACEBACK_INFIX_ALL_STATS = {"device": 0}
 
 
 def _cigar_of_steps(steps):
@@ -184,3 +186,23 @@ def edlib_traceback_infix(x, y, k=1):
     if rows[0, 0] < 0:
         return -1, [], None
     return int(rows[0, 0]), [(int(rows[0, 1]), int(rows[0, 2]))], "".join("%d%s" % (o >> 4, "=XID"[o & 15]) for o in ops.tolist())
+
+
+def edlib_traceback_infix_all(x, y, k=1):
+    """(editDistance, locations, cigar) of edlib.align(x, y, mode="HW", task="path", k=k) with ALL its locations: every end position of y
+    at which x aligns with the best distance, in ascending order of the end, each as (start, end) with the smallest start of that
+    distance (SeqStore.hw_locations) -- what primer, barcode, poly-A and repeat searches ask.  locations[0] is the one location
+    edlib_traceback_infix reports, and the cigar belongs to it (edlib's convention; SeqStore.hw_path_pairs).  k None or negative:
+    unbounded.  Above k, and for an empty x or y: (-1, [], None).  GPU only and at most four distinct symbols, like
+    edlib_traceback_infix; a pair whose band max(len(y) - len(x), 0) + 2 k + 1 exceeds 512 diagonals raises IsoconError."""
+    kk = None if k is None or k < 0 else [int(k)]
+    st = SeqStore([x, y])
+    try:
+        ed, loc_ptr, locs = st.hw_locations([0], [1], kk)
+        ops = st.hw_path_pairs([0], [1], kk)[1] if ed[0] >= 0 else None
+    finally:
+        st.close()
+    TRACEBACK_INFIX_ALL_STATS["device"] += 1
+    if ed[0] < 0:
+        return -1, [], None
+    return int(ed[0]), [(int(s), int(e)) for s, e in locs[int(loc_ptr[0]):int(loc_ptr[1])].tolist()], "".join("%d%s" % (o >> 4, "=XID"[o & 15]) for o in ops.tolist())

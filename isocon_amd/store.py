@@ -170,6 +170,37 @@ class SeqStore(object):
             out = (rows, ops[:int(ops_ptr[n])], ops_ptr)
             return out + (ms.value,) if return_ms else out
 
+    def hw_locations(self, q, t, k=None, return_ms=False):
+        """Every best location of q[p] inside t[p], the `locations` of edlib.align(q[p], t[p], mode="HW", task="path", k[p])
+        (isocon_hw_locations): (ed int32[n] -- distance or -1 --, loc_ptr uint64[n + 1], locs int32[L, 2]); a hit p owns the rows
+        locs[loc_ptr[p]:loc_ptr[p + 1]] = (start, end), one per end column that attains the distance, in ascending order of the end, each
+        with the smallest start of that distance; the first is the (start, end) of hw_pairs.  k: a scalar or one value per pair; None or a
+        negative value: unbounded (sent as len(q[p])).  The limits are those of hw_pairs: at most four symbols, bands up to 512 diagonals."""
+        q = np.ascontiguousarray(q, dtype=np.uint32)
+        t = np.ascontiguousarray(t, dtype=np.uint32)
+        if len(q) != len(t):
+            raise ValueError("pair arrays differ in length")
+        n = len(q)
+        # (an id out of range is the library's to refuse)
+        qlen = np.take(np.asarray(self.lens, dtype=np.int64), q, mode="clip") if self.n else np.zeros(n, dtype=np.int64)
+        kk = np.broadcast_to(np.asarray(-1 if k is None else k, dtype=np.int64), q.shape)
+        kk = np.ascontiguousarray(np.where(kk < 0, qlen, kk).clip(max=2 ** 31 - 1), dtype=np.int32)
+        ed = np.full(n, -1, dtype=np.int32)
+        loc_ptr = np.zeros(n + 1, dtype=np.uint64)
+        cap = 4 * n + 1024
+        needed = ctypes.c_uint64(0)
+        ms = ctypes.c_float(0)
+        while True:
+            locs = np.empty((cap, 2), dtype=np.int32)
+            rc = self._L.isocon_hw_locations(self._h, _ptr(q, _lib.u32p), _ptr(t, _lib.u32p), _ptr(kk, _lib.i32p), n, _ptr(ed, _lib.i32p),
+                                             _ptr(loc_ptr, _lib.u64p), _ptr(locs, _lib.i32p), cap, ctypes.byref(needed), ctypes.byref(ms))
+            if rc == _lib.ISOCON_E_CAPACITY:
+                cap = int(needed.value) + 16
+                continue
+            _lib.check(rc, "isocon_hw_locations")
+            out = (ed, loc_ptr, locs[:int(loc_ptr[n])])
+            return out + (ms.value,) if return_ms else out
+
     def qgram_bound_pairs(self, a, b):
         """Lower bounds of ed(a[i], b[i]) from q-gram count profiles (csrc/qgram_mm.hpp) -- the pre-filter of the NN main pass."""
         a = np.ascontiguousarray(a, dtype=np.uint32)
@@ -672,6 +703,16 @@ def hw_last_stats():
     _lib.load().isocon_hw_last_stats(out, 17)
     keys = ("route", "retried_host", "pairs", "need_kernel", "hits") + tuple(
         "%s_w%d" % (name, w) for name in ("locate_tiles", "finish_tiles", "finish_grid") for w in (1, 2, 4, 8))
+    return {key: int(v) for key, v in zip(keys, out)}
+
+
+def hw_locations_last_stats():
+    """what this thread's most recent hw_locations call did (isocon_hw_locations_last_stats, include/isocon_hip.h): pairs, hits, locations,
+    host_cuts, and per class of 1, 2, 4, 8 window words the tiles of the distance stage, of an ends run and of the start stage"""
+    out = (ctypes.c_double * 16)()
+    _lib.load().isocon_hw_locations_last_stats(out, 16)
+    keys = ("pairs", "hits", "locations", "host_cuts") + tuple(
+        "%s_w%d" % (name, w) for name in ("locate_tiles", "ends_tiles", "starts_tiles") for w in (1, 2, 4, 8))
     return {key: int(v) for key, v in zip(keys, out)}
 
 
