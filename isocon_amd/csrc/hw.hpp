@@ -103,7 +103,7 @@ __global__ __launch_bounds__(64) void k_hw_finish(DevStore S, HwTileIn in, const
                                                    uint32_t trace_cols, int32_t *__restrict__ out)
 {
     const int lane = threadIdx.x;
-    // the workgroup's store: checkpoints (W <= 2) or every column's vectors (nn_host's hw_finish_store_bytes is the same formula)
+    // the workgroup's store: checkpoints (W <= 2) or every column's vectors (hw_plan.hpp's hw_finish_store_bytes is the same formula)
     uint64_t *trace = trace_all + (size_t)blockIdx.x * (W <= 2 ? ((size_t)trace_cols / HW_SEG + 2) : ((size_t)trace_cols + 1)) * 2 * W * 64;
     const uint64_t *planes = S.planes;
     const uint32_t *pw = reinterpret_cast<const uint32_t *>(planes);

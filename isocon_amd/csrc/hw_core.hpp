@@ -49,6 +49,9 @@ struct HwLane {
 // tile geometry from the lanes' extremes (device: wave reductions; emulator: loops)
 ISO_HD int32_t hw_locate_a0(int32_t delta_max, int32_t k_max) { return -((delta_max > 0 ? delta_max : 0) + k_max); }
 ISO_HD int32_t hw_locate_rows(int32_t delta_max, int32_t k_max) { return (delta_max > 0 ? delta_max : 0) + 2 * k_max + 1; }
+// window words of a band of `rows` diagonals (0: beyond the widest class) and the class (0 .. 3) of 1, 2, 4, 8 words
+ISO_HD int hwt_words(int32_t rows) { return rows <= 64 ? 1 : rows <= 128 ? 2 : rows <= 256 ? 4 : rows <= 512 ? 8 : 0; }
+ISO_HD uint32_t hwt_class(int words) { return words == 1 ? 0u : words == 2 ? 1u : words == 4 ? 2u : 3u; }
 
 ISO_HD uint64_t hw_brev64(uint64_t x)
 {

@@ -13,7 +13,7 @@ inline bool hwf_is_narrow(int32_t len_q, int32_t len_t, int32_t kk)
 {
     const int32_t delta = len_t - len_q;
     if (delta < -kk || len_q == 0 || len_t == 0) return true;
-    return hw_words(hw_locate_rows(delta, kk)) != 0;
+    return hwt_words(hw_locate_rows(delta, kk)) != 0;
 }
 
 int hwf_pairs(isocon_store *s, const std::vector<uint32_t> &q, const std::vector<uint32_t> &t, const std::vector<int32_t> &k, int32_t *rows, float *kernel_ms)

@@ -1,9 +1,8 @@
-// hw_host.inc -- host side of isocon_hw_pairs (included by isocon_hip.hip): tiles of one query x up to 64 targets for the
-// bit-parallel kernels of hw.hpp.
+// hw_host.inc -- host side of isocon_hw_pairs (included by isocon_hip.hip), and the driver every entry on the banded infix kernels of
+// hw.hpp and hw_loc.hpp runs on (HwDriver: the tiles of a stage, one launch per class, the finish stage).  Tiles are one query x up to 64
+// targets; what the host decides about them without a device (the greedy cut, the finish grid) is in hw_plan.hpp.
 
 namespace {
-
-inline int hw_words(int32_t rows) { return rows <= 64 ? 1 : rows <= 128 ? 2 : rows <= 256 ? 4 : rows <= 512 ? 8 : 0; }
 
 // isocon_hw_last_stats: the calling thread's last isocon_hw_pairs call (and what hw_pairs_device_core did for the entries that share it).
 // HS_LOCATE / HS_FINISH / HS_GRID + c: class c = 0 .. 3 (1, 2, 4, 8 window words).  -1: not counted on that route.
@@ -16,80 +15,162 @@ inline void hw_stats_route(int route, uint64_t n_pairs)
     g_hw_stats[HS_PAIRS] = (double)n_pairs;
 }
 
-// Tiles of the pairs `idx` (any order): pairs are grouped by (words needed, query) with two counting sorts, a group is cut
-// into tiles of at most 64 lanes whose COMMON window (largest length difference and largest threshold of the tile) still
-// fits the class.  rows(p) = rows of the band pair p needs on its own; fits(dmax, kmax, W) = do these extremes fit W words.
-struct HwTiles {
-    std::vector<uint32_t> tile_q[4], lane_pair[4];      // per class W = 1, 2, 4, 8
-};
-
-template <class Words, class Fits>
-void hw_build_tiles(const std::vector<uint32_t> &idx, const uint32_t *q, uint32_t nseq, Words words_of, Fits fits, HwTiles &out)
+// f(std::integral_constant<int, W>()) for the window words W = 1, 2, 4, 8 of class c = 0 .. 3
+template <class F>
+int hw_for_words(int c, F f)
 {
-    // stable counting sort by query, then a stable split by class
-    std::vector<uint32_t> first((size_t)nseq + 1, 0);
-    for (uint32_t p : idx) ++first[(size_t)q[p] + 1];
-    for (uint32_t i = 0; i < nseq; ++i) first[i + 1] += first[i];
-    std::vector<uint32_t> byq(idx.size());
-    for (uint32_t p : idx) byq[first[q[p]]++] = p;
-    static const int cls_of[9] = {-1, 0, 1, -1, 2, -1, -1, -1, 3};
-    for (int c = 0; c < 4; ++c) {
-        const int Wc = 1 << c;
-        std::vector<uint32_t> &tq = out.tile_q[c], &lp = out.lane_pair[c];
-        uint32_t cur_q = 0xffffffffu;
-        int32_t dmax = 0, kmax = 0;
-        size_t fill = 64;
-        for (uint32_t p : byq) {
-            if (cls_of[words_of(p)] != c) continue;
-            int32_t d2 = dmax, k2 = kmax;
-            const bool same = q[p] == cur_q && fill < 64 && fits(p, d2, k2, Wc);
-            if (!same) {
-                while (fill < 64 && !tq.empty()) { lp.push_back(0xffffffffu); ++fill; }
-                tq.push_back(q[p]);
-                cur_q = q[p];
-                fill = 0;
-                d2 = -(1 << 30); k2 = 0;
-                fits(p, d2, k2, Wc);
-            }
-            dmax = d2; kmax = k2;
-            lp.push_back(p);
-            ++fill;
-        }
-        while (fill < 64 && !tq.empty()) { lp.push_back(0xffffffffu); ++fill; }
+    switch (c) {
+    case 0: return f(std::integral_constant<int, 1>());
+    case 1: return f(std::integral_constant<int, 2>());
+    case 2: return f(std::integral_constant<int, 4>());
+    default: return f(std::integral_constant<int, 8>());
     }
 }
 
-template <int W>
-int hw_launch_locate(isocon_store *st, const HwTileIn &in, int32_t *d_he)
+int hw_launch_locate(isocon_store *st, int c, const HwTileIn &in, int32_t *d_he)
 {
-    hipLaunchKernelGGL((k_hw_locate<W>), dim3((in.n_tiles + 3) / 4), dim3(256), 0, 0, st->dev, in, d_he);
-    ISO_HIP_CHECK(hipGetLastError());
+    return hw_for_words(c, [&](auto w) -> int {
+        hipLaunchKernelGGL((k_hw_locate<decltype(w)::value>), dim3((in.n_tiles + 3) / 4), dim3(256), 0, 0, st->dev, in, d_he);
+        ISO_HIP_CHECK(hipGetLastError());
+        return ISOCON_OK;
+    });
+}
+
+int hw_launch_finish(isocon_store *st, int c, const HwTileIn &in, uint32_t grid, const int32_t *d_he, uint64_t *d_trace, uint32_t trace_cols, int32_t *d_out)
+{
+    return hw_for_words(c, [&](auto w) -> int {
+        constexpr int W = decltype(w)::value;
+        hipLaunchKernelGGL((k_hw_finish<W>), dim3(grid), dim3(64), hw_finish_lds(W), 0, st->dev, in, d_he, d_trace, trace_cols, d_out);
+        ISO_HIP_CHECK(hipGetLastError());
+        return ISOCON_OK;
+    });
+}
+
+// What the error flags of the tile builder and the kernels (HwTileCounters::flags) mean to `entry`.  retry_host: where to say that only the
+// host's greedy cut can form the tiles; nullptr: the caller deals with HWT_ERR_TILE_BAND itself.
+int hw_flag_error(uint32_t flags, const char *entry, bool *retry_host)
+{
+    if (flags & HWT_ERR_INDEX) return ISOCON_E_ARG;
+    if (flags & HWT_ERR_K_NEGATIVE) { g_last_error = std::string(entry) + ": k must be >= 0 (the band is derived from it)"; return ISOCON_E_ARG; }
+    if (flags & HWT_ERR_K_LARGE) return ISOCON_E_UNSUPPORTED;
+    if (flags & HWT_ERR_BAND) { g_last_error = std::string(entry) + ": a pair's band needs more than 512 diagonals (not supported)"; return ISOCON_E_UNSUPPORTED; }
+    if (retry_host && (flags & HWT_ERR_TILE_BAND)) { *retry_host = true; return ISOCON_E_UNSUPPORTED; }
+    if (flags & HWT_ERR_STATUS) { g_last_error = std::string(entry) + ": internal status from a kernel"; return ISOCON_E_HIP; }
     return ISOCON_OK;
 }
 
-// k_hw_finish<1|2> keeps checkpoints of the band state (every HW_SEG-th column) in its per-workgroup store and walks on segments
-// recomputed into LDS; the wider classes store every column.
-inline size_t hw_finish_lds(int Wc) { return Wc == 2 ? (size_t)HW_SEG * 2 * Wc * 64 * 8 : 0; }          // (one word: the segment stays in registers)
-inline uint64_t hw_finish_store_bytes(int Wc, uint32_t trace_cols)
-{
-    return Wc <= 2 ? ((uint64_t)trace_cols / HW_SEG + 2) * 2 * Wc * 64 * 8 : ((uint64_t)trace_cols + 1) * 2 * Wc * 64 * 8;
-}
-inline uint32_t hw_finish_grid_cap(int Wc) { return Wc == 2 ? (uint32_t)(256 * (160 * 1024 / (hw_finish_lds(Wc) + 256))) : 4096u; }
+// the tiles of one stage: lists per class in device memory (HwDriver::build_device) or cut on the host (HwDriver::cut_host)
+struct HwStageTiles {
+    bool host = false;
+    HwTileCounters ctr{};
+    HwTiles cut;
+    uint32_t count(int c) const { return host ? (uint32_t)cut.tile_q[c].size() : ctr.cls[c]; }
+};
 
-template <int W>
-int hw_launch_finish(isocon_store *st, const HwTileIn &in, uint32_t grid, const int32_t *d_he, uint64_t *d_trace, uint32_t trace_cols, int32_t *d_out)
-{
-    hipLaunchKernelGGL((k_hw_finish<W>), dim3(grid), dim3(64), hw_finish_lds(W), 0, st->dev, in, d_he, d_trace, trace_cols, d_out);
-    ISO_HIP_CHECK(hipGetLastError());
-    return ISOCON_OK;
-}
+// The stages of one call.  A call that builds tiles on the device sizes the builder's arrays first (size()); its kernels then report
+// through the counters' flag word and nothing fences its launches.  Without size() -- the host route of isocon_hw_pairs, which reads every
+// row's status and waits behind every launch -- the kernels get no flag word.
+struct HwDriver {
+    isocon_store *s;
+    DevBuf d_tq, d_lp, d_key, d_hist, d_cursor, d_tbase, d_cls, d_ctr, d_trace;
+    uint32_t n_keys = 0, max_tiles = 0;
+    HwDriver(isocon_store *st, ScratchPool *pl)
+        : s(st), d_tq(pl, SLOT_HW_TILEQ), d_lp(pl, SLOT_HW_LANES), d_key(pl, SLOT_HW_KEY), d_hist(pl, SLOT_HW_HIST), d_cursor(pl, SLOT_HW_CURSOR),
+          d_tbase(pl, SLOT_HW_TBASE), d_cls(pl, SLOT_HW_CLS), d_ctr(pl, SLOT_HW_CTR), d_trace(pl, SLOT_HW_TRACE) {}
+    uint32_t *flags() { return d_ctr.p ? &d_ctr.as<HwTileCounters>()->flags : nullptr; }
 
-}  // namespace
+    // the builder's arrays for a list of `count` entries; ISOCON_E_UNSUPPORTED: more keys or tiles than it can index
+    int size(uint64_t count)
+    {
+        if ((uint64_t)s->dev.n * 4 >= 0xfffffff0ull) return ISOCON_E_UNSUPPORTED;
+        n_keys = s->dev.n * 4u;
+        const uint64_t mt = count / 64 + std::min<uint64_t>(count, n_keys) + 1;
+        if (mt > 0x7fffff00ull) return ISOCON_E_UNSUPPORTED;
+        max_tiles = (uint32_t)mt;
+        int rc;
+        if ((rc = d_key.alloc(count * 4)) || (rc = d_hist.alloc((size_t)n_keys * 4)) || (rc = d_cursor.alloc((size_t)n_keys * 4)) ||
+            (rc = d_tbase.alloc(((size_t)n_keys + 1) * 4)) || (rc = d_tq.alloc((size_t)max_tiles * 4)) || (rc = d_lp.alloc((size_t)max_tiles * 256)) ||
+            (rc = d_cls.alloc((size_t)max_tiles * 16)) || (rc = d_ctr.alloc(sizeof(HwTileCounters))))
+            return rc;
+        return ISOCON_OK;
+    }
 
-namespace {
+    // tiles of the list (d_q, d_t, d_k) on the device (hw_tiles.hpp; STAGE names the builder's rule), tl.ctr = the stage's counters
+    template <int STAGE>
+    int build_device(uint64_t count, const uint32_t *d_q, const uint32_t *d_t, const int32_t *d_k, int32_t *d_he, int32_t *d_out, HwStageTiles &tl)
+    {
+        HwTileCounters *ctr = d_ctr.as<HwTileCounters>();
+        uint32_t *hist = d_hist.as<uint32_t>(), *cursor = d_cursor.as<uint32_t>(), *tbase = d_tbase.as<uint32_t>(), *tq = d_tq.as<uint32_t>(), *lp = d_lp.as<uint32_t>();
+        tl.host = false;
+        ISO_HIP_CHECK(hipMemsetAsync(hist, 0, (size_t)n_keys * 4, 0));
+        ISO_HIP_CHECK(hipMemsetAsync(cursor, 0, (size_t)n_keys * 4, 0));
+        ISO_HIP_CHECK(hipMemsetAsync(ctr, 0, sizeof(HwTileCounters), 0));
+        ISO_HIP_CHECK(hipMemsetAsync(lp, 0xff, (size_t)max_tiles * 256, 0));
+        const unsigned pb = (unsigned)((count + 255) / 256);
+        hipLaunchKernelGGL((k_hwt_keys<STAGE>), dim3(pb), dim3(256), 0, 0, s->dev, d_q, d_t, d_k, (unsigned long long)count, d_he, d_out, d_key.as<uint32_t>(), hist, ctr);
+        if (int rc = device_exscan<6, uint32_t>(&g_scratch, hist, n_keys, tbase)) return rc;
+        hipLaunchKernelGGL(k_hwt_scatter, dim3(pb), dim3(256), 0, 0, d_key.as<uint32_t>(), (unsigned long long)count, tbase, cursor, tq, lp);
+        hipLaunchKernelGGL((k_hwt_classes<STAGE>), dim3((max_tiles + 3) / 4), dim3(256), 0, 0, s->dev, tq, lp, d_t, d_k, max_tiles, tbase + n_keys, d_cls.as<uint32_t>(), ctr);
+        ISO_HIP_CHECK(hipGetLastError());
+        return read_counters(tl.ctr);
+    }
+    int read_counters(HwTileCounters &ctr)
+    {
+        ISO_HIP_CHECK(hipMemcpy(&ctr, d_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost));
+        return ISOCON_OK;
+    }
 
-// Tiles built on the host (two counting sorts and a greedy cut, hw_build_tiles): small calls, and calls where a run of 64 pairs of one
-// query has a common window wider than 512 diagonals although every pair fits on its own.
+    // tiles of the pairs `idx` of the caller's arrays, cut on the host (two counting sorts and a greedy cut, hw_build_tiles): small calls,
+    // and calls where a run of 64 pairs of one query has a common window wider than 512 diagonals although every pair fits on its own
+    template <class Rule>
+    void cut_host(const std::vector<uint32_t> &idx, const uint32_t *q, const Rule &rule, HwStageTiles &tl)
+    {
+        tl.host = true;
+        tl.cut = HwTiles();
+        hw_build_tiles(idx, q, s->dev.n, rule, tl.cut);
+    }
+
+    // launch(c, in) for every class c that has tiles; stat[c] = its tiles (stat may be nullptr)
+    template <class Launch>
+    int for_classes(const HwStageTiles &tl, const uint32_t *d_t, const int32_t *d_k, double *stat, Launch launch)
+    {
+        for (int c = 0; c < 4; ++c) {
+            if (stat) stat[c] = (double)tl.count(c);
+            if (!tl.count(c)) continue;
+            HwTileIn in{};
+            in.pt = d_t; in.pk = d_k; in.n_tiles = tl.count(c); in.flags = flags();
+            int rc;
+            if (tl.host) {
+                const std::vector<uint32_t> &tq = tl.cut.tile_q[c], &lp = tl.cut.lane_pair[c];
+                if (flags()) ISO_HIP_CHECK(device_wait());          // the launch before may still read the tiles these replace
+                if ((rc = d_tq.upload(tq.data(), tq.size() * 4)) || (rc = d_lp.upload(lp.data(), lp.size() * 4))) return rc;
+            } else in.tile_list = d_cls.as<uint32_t>() + (size_t)c * max_tiles;
+            in.tile_q = d_tq.as<uint32_t>(); in.lane_pair = d_lp.as<uint32_t>();
+            if ((rc = launch(c, in))) return rc;
+        }
+        return ISOCON_OK;
+    }
+
+    // START + TRACE + walk for the hits of he (smallest start, terminal insertion runs), one launch per class of `tl`; stats = g_hw_stats
+    int finish_stage(const HwStageTiles &tl, const uint32_t *d_t, const int32_t *d_k, const int32_t *d_he, int32_t *d_out, EventTimer &tm, double *stats)
+    {
+        const uint32_t trace_cols = (uint32_t)s->maxlen + 1;
+        return for_classes(tl, d_t, d_k, stats + HS_FINISH, [&](int c, const HwTileIn &in) -> int {
+            size_t free_b = 0, total_b = 0;
+            if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = ~(size_t)0;          // (then the fixed bound alone)
+            const uint32_t grid = hw_finish_grid(in.n_tiles, 1 << c, trace_cols, free_b);
+            stats[HS_GRID + c] = (double)grid;
+            int rc;
+            if ((rc = d_trace.alloc((size_t)grid * hw_finish_store_bytes(1 << c, trace_cols)))) return rc;
+            tm.start();
+            if ((rc = hw_launch_finish(s, c, in, grid, d_he, d_trace.as<uint64_t>(), trace_cols, d_out))) return rc;
+            tm.stop();                                  // also the fence before the column store is reused / regrown
+            return ISOCON_OK;
+        });
+    }
+};
+
+// Tiles cut on the host: small calls, and the retry of a call whose tiles the device could not form.
 int hw_pairs_host_tiles(isocon_store *s, const uint32_t *q, const uint32_t *t, const int32_t *k, uint64_t n_pairs, int32_t *out, float *kernel_ms)
 {
     const uint32_t n = s->dev.n;
@@ -107,7 +188,7 @@ int hw_pairs_host_tiles(isocon_store *s, const uint32_t *q, const uint32_t *t, c
         o[0] = -1; o[1] = -1; o[2] = -1; o[3] = 0; o[4] = 0;
         const int32_t delta = lens[t[p]] - lens[q[p]];
         if (delta < -kk || lens[q[p]] == 0 || lens[t[p]] == 0) continue;
-        if (!hw_words(hw_locate_rows(delta, kk))) {
+        if (!hwt_words(hw_locate_rows(delta, kk))) {
             g_last_error = "isocon_hw_pairs: band of " + std::to_string(hw_locate_rows(delta, kk)) + " diagonals not supported (limit 512)";
             return ISOCON_E_UNSUPPORTED;
         }
@@ -118,46 +199,22 @@ int hw_pairs_host_tiles(isocon_store *s, const uint32_t *q, const uint32_t *t, c
     HostClock clk;
     clk.lap("hw: classify");
     ScratchPool *pl = &g_scratch;
-    DevBuf d_t(pl, SLOT_HW_T), d_k(pl, SLOT_HW_K), d_he(pl, SLOT_HW_Q), d_out(pl, SLOT_HW_OUT), d_trace(pl, SLOT_HW_TRACE);
-    DevBuf d_tq(pl, SLOT_HW_TILEQ), d_lp(pl, SLOT_HW_LANES);
+    HwDriver drv(s, pl);
+    DevBuf d_t(pl, SLOT_HW_T), d_k(pl, SLOT_HW_K), d_he(pl, SLOT_HW_Q), d_out(pl, SLOT_HW_OUT);
     int rc;
-    if ((rc = d_t.alloc(n_pairs * 4)) || (rc = d_k.alloc(n_pairs * 4)) || (rc = d_he.alloc(n_pairs * 8))) return rc;
-    ISO_HIP_CHECK(copy_h2d(d_t.p, t, n_pairs * 4));
-    ISO_HIP_CHECK(copy_h2d(d_k.p, k, n_pairs * 4));
+    if ((rc = d_t.upload(t, n_pairs * 4)) || (rc = d_k.upload(k, n_pairs * 4)) || (rc = d_he.alloc(n_pairs * 8))) return rc;
     EventTimer tm;
-    auto upload_tiles = [&](const std::vector<uint32_t> &tq, const std::vector<uint32_t> &lp, HwTileIn &in) -> int {
-        int r;
-        if ((r = d_tq.alloc(tq.size() * 4)) || (r = d_lp.alloc(lp.size() * 4))) return r;
-        ISO_HIP_CHECK(copy_h2d(d_tq.p, tq.data(), tq.size() * 4));
-        ISO_HIP_CHECK(copy_h2d(d_lp.p, lp.data(), lp.size() * 4));
-        in.tile_q = d_tq.as<uint32_t>(); in.lane_pair = d_lp.as<uint32_t>();
-        in.pt = d_t.as<uint32_t>(); in.pk = d_k.as<int32_t>(); in.n_tiles = (uint32_t)tq.size();
-        return ISOCON_OK;
-    };
+    HwStageTiles tiles;
     // ---- LOCATE: distance and first end of every pair ----
-    {
-        HwTiles tiles;
-        hw_build_tiles(run, q, n,
-                       [&](uint32_t p) { return hw_words(hw_locate_rows(lens[t[p]] - lens[q[p]], k[p])); },
-                       [&](uint32_t p, int32_t &dmax, int32_t &kmax, int Wc) {
-                           const int32_t d2 = std::max(dmax, lens[t[p]] - lens[q[p]]), k2 = std::max(kmax, k[p]);
-                           if (hw_locate_rows(d2, k2) > 64 * Wc) return false;
-                           dmax = d2; kmax = k2;
-                           return true;
-                       }, tiles);
-        clk.lap("hw: locate tiles (host)");
-        for (int c = 0; c < 4; ++c) {
-            g_hw_stats[HS_LOCATE + c] = (double)tiles.tile_q[c].size();
-            if (tiles.tile_q[c].empty()) continue;
-            HwTileIn in{};
-            if ((rc = upload_tiles(tiles.tile_q[c], tiles.lane_pair[c], in))) return rc;
-            tm.start();
-            rc = c == 0 ? hw_launch_locate<1>(s, in, d_he.as<int32_t>()) : c == 1 ? hw_launch_locate<2>(s, in, d_he.as<int32_t>())
-               : c == 2 ? hw_launch_locate<4>(s, in, d_he.as<int32_t>()) : hw_launch_locate<8>(s, in, d_he.as<int32_t>());
-            if (rc) return rc;
-            tm.stop();
-        }
-    }
+    drv.cut_host(run, q, HwLocateCut{lens.data(), q, t, k}, tiles);
+    clk.lap("hw: locate tiles (host)");
+    if ((rc = drv.for_classes(tiles, d_t.as<uint32_t>(), d_k.as<int32_t>(), g_hw_stats + HS_LOCATE, [&](int c, const HwTileIn &in) -> int {
+             tm.start();
+             if (int r = hw_launch_locate(s, c, in, d_he.as<int32_t>())) return r;
+             tm.stop();
+             return ISOCON_OK;
+         })))
+        return rc;
     clk.lap("hw: locate kernels");
     std::vector<int32_t> he(n_pairs * 2);
     ISO_HIP_CHECK(copy_d2h(he.data(), d_he.p, n_pairs * 8));
@@ -171,43 +228,11 @@ int hw_pairs_host_tiles(isocon_store *s, const uint32_t *q, const uint32_t *t, c
     clk.lap("hw: he download + hit list");
     g_hw_stats[HS_HITS] = (double)hits.size();
     if (hits.empty()) { if (kernel_ms) *kernel_ms = tm.total; return ISOCON_OK; }
-    // ---- START + TRACE + walk for the hits: smallest start, terminal insertion runs ----
+    // ---- START + TRACE + walk for the hits ----
     if ((rc = d_out.alloc(n_pairs * 20))) return rc;
-    {
-        HwTiles tiles;
-        hw_build_tiles(hits, q, n,
-                       [&](uint32_t p) { return hw_words(2 * k[p] + 1); },
-                       [&](uint32_t p, int32_t &dmax, int32_t &kmax, int Wc) {
-                           const int32_t k2 = std::max(kmax, k[p]);
-                           if (2 * k2 + 1 > 64 * Wc) return false;
-                           dmax = 0; kmax = k2;
-                           return true;
-                       }, tiles);
-        clk.lap("hw: finish tiles (host)");
-        const uint32_t trace_cols = (uint32_t)s->maxlen + 1;
-        for (int c = 0; c < 4; ++c) {
-            g_hw_stats[HS_FINISH + c] = (double)tiles.tile_q[c].size();
-            if (tiles.tile_q[c].empty()) continue;
-            const int Wc = 1 << c;
-            HwTileIn in{};
-            if ((rc = upload_tiles(tiles.tile_q[c], tiles.lane_pair[c], in))) return rc;
-            // one wavefront per tile in flight, each with its own column store: as many as 16 per CU, bounded by memory
-            const uint64_t per_block = hw_finish_store_bytes(Wc, trace_cols);
-            size_t free_b = 0, total_b = 0;
-            uint64_t budget = (uint64_t)12 << 30;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = std::min<uint64_t>(budget, (uint64_t)free_b / 3);
-            const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(in.n_tiles, hw_finish_grid_cap(Wc)), budget / per_block));
-            g_hw_stats[HS_GRID + c] = (double)grid;
-            if ((rc = d_trace.alloc((size_t)grid * per_block))) return rc;
-            tm.start();
-            rc = c == 0 ? hw_launch_finish<1>(s, in, grid, d_he.as<int32_t>(), d_trace.as<uint64_t>(), trace_cols, d_out.as<int32_t>())
-               : c == 1 ? hw_launch_finish<2>(s, in, grid, d_he.as<int32_t>(), d_trace.as<uint64_t>(), trace_cols, d_out.as<int32_t>())
-               : c == 2 ? hw_launch_finish<4>(s, in, grid, d_he.as<int32_t>(), d_trace.as<uint64_t>(), trace_cols, d_out.as<int32_t>())
-                        : hw_launch_finish<8>(s, in, grid, d_he.as<int32_t>(), d_trace.as<uint64_t>(), trace_cols, d_out.as<int32_t>());
-            if (rc) return rc;
-            tm.stop();                                  // also the fence before the column store is reused / regrown
-        }
-    }
+    drv.cut_host(hits, q, HwFinishCut{k}, tiles);
+    clk.lap("hw: finish tiles (host)");
+    if ((rc = drv.finish_stage(tiles, d_t.as<uint32_t>(), d_k.as<int32_t>(), d_he.as<int32_t>(), d_out.as<int32_t>(), tm, g_hw_stats))) return rc;
     clk.lap("hw: finish kernels");
     // only the hits' rows were written on the device: fetch the whole array once and pick them (one large copy beats many small)
     std::vector<int32_t> res(n_pairs * 5);
@@ -223,25 +248,6 @@ int hw_pairs_host_tiles(isocon_store *s, const uint32_t *q, const uint32_t *t, c
     return ISOCON_OK;
 }
 
-template <int STAGE>
-int hw_device_tiles(isocon_store *st, uint64_t n_pairs, const uint32_t *d_q, const uint32_t *d_t, const int32_t *d_k, int32_t *d_he, int32_t *d_out,
-                    uint32_t *d_key, uint32_t *d_hist, uint32_t *d_cursor, uint32_t *d_tbase, uint32_t n_keys, uint32_t *d_tq, uint32_t *d_lp, uint32_t max_tiles,
-                    uint32_t *d_cls, HwTileCounters *d_ctr, HwTileCounters &ctr)
-{
-    ISO_HIP_CHECK(hipMemsetAsync(d_hist, 0, (size_t)n_keys * 4, 0));
-    ISO_HIP_CHECK(hipMemsetAsync(d_cursor, 0, (size_t)n_keys * 4, 0));
-    ISO_HIP_CHECK(hipMemsetAsync(d_ctr, 0, sizeof(HwTileCounters), 0));
-    ISO_HIP_CHECK(hipMemsetAsync(d_lp, 0xff, (size_t)max_tiles * 256, 0));
-    const unsigned pb = (unsigned)((n_pairs + 255) / 256);
-    hipLaunchKernelGGL((k_hwt_keys<STAGE>), dim3(pb), dim3(256), 0, 0, st->dev, d_q, d_t, d_k, (unsigned long long)n_pairs, d_he, d_out, d_key, d_hist, d_ctr);
-    { int rc = device_exscan<6, uint32_t>(&g_scratch, d_hist, n_keys, d_tbase); if (rc) return rc; }
-    hipLaunchKernelGGL(k_hwt_scatter, dim3(pb), dim3(256), 0, 0, d_key, (unsigned long long)n_pairs, d_tbase, d_cursor, d_tq, d_lp);
-    hipLaunchKernelGGL((k_hwt_classes<STAGE>), dim3((max_tiles + 3) / 4), dim3(256), 0, 0, st->dev, d_tq, d_lp, d_t, d_k, max_tiles, d_tbase + n_keys, d_cls, d_ctr);
-    ISO_HIP_CHECK(hipGetLastError());
-    ISO_HIP_CHECK(hipMemcpy(&ctr, d_ctr, sizeof(ctr), hipMemcpyDeviceToHost));
-    return ISOCON_OK;
-}
-
 // The rows of pair lists that are already in device memory (d_q, d_t, d_k: n_pairs entries each), tiles built on the device
 // (hw_tiles.hpp): *d_rows = the (n_pairs, 5) result in the pool's SLOT_HW_OUT, good until the next call that takes that slot.
 // Returns ISOCON_E_UNSUPPORTED with *retry_host set when only the host's greedy cut can form the tiles.
@@ -249,93 +255,35 @@ int hw_pairs_device_core(isocon_store *s, const uint32_t *d_q, const uint32_t *d
                          bool *retry_host)
 {
     *retry_host = false;
-    const uint32_t n = s->dev.n;
     hw_stats_route(1, n_pairs);
     g_hw_stats[HS_NEED_KERNEL] = g_hw_stats[HS_HITS] = -1;          // (counted by hw_pairs_device_tiles, which has the lists on the host)
-    if ((uint64_t)n * 4 >= 0xfffffff0ull) { *retry_host = true; return ISOCON_E_UNSUPPORTED; }
     HostClock clk;
     ScratchPool *pl = &g_scratch;
-    DevBuf d_he(pl, SLOT_HW_Q), d_out(pl, SLOT_HW_OUT), d_trace(pl, SLOT_HW_TRACE);
-    DevBuf d_tq(pl, SLOT_HW_TILEQ), d_lp(pl, SLOT_HW_LANES), d_key(pl, SLOT_HW_KEY), d_hist(pl, SLOT_HW_HIST), d_cursor(pl, SLOT_HW_CURSOR),
-        d_tbase(pl, SLOT_HW_TBASE), d_cls(pl, SLOT_HW_CLS), d_ctr(pl, SLOT_HW_CTR);
-    const uint32_t n_keys = n * 4u;
-    const uint64_t max_tiles64 = n_pairs / 64 + std::min<uint64_t>(n_pairs, n_keys) + 1;
-    if (max_tiles64 > 0x7fffff00ull) { *retry_host = true; return ISOCON_E_UNSUPPORTED; }
-    const uint32_t max_tiles = (uint32_t)max_tiles64;
+    HwDriver drv(s, pl);
+    DevBuf d_he_buf(pl, SLOT_HW_Q), d_out_buf(pl, SLOT_HW_OUT);
     int rc;
-    if ((rc = d_he.alloc(n_pairs * 8)) ||
-        (rc = d_out.alloc(n_pairs * 20)) || (rc = d_key.alloc(n_pairs * 4)) || (rc = d_hist.alloc((size_t)n_keys * 4)) || (rc = d_cursor.alloc((size_t)n_keys * 4)) ||
-        (rc = d_tbase.alloc(((size_t)n_keys + 1) * 4)) || (rc = d_tq.alloc((size_t)max_tiles * 4)) || (rc = d_lp.alloc((size_t)max_tiles * 256)) ||
-        (rc = d_cls.alloc((size_t)max_tiles * 16)) || (rc = d_ctr.alloc(sizeof(HwTileCounters))))
-        return rc;
+    if ((rc = drv.size(n_pairs))) { *retry_host = rc == ISOCON_E_UNSUPPORTED; return rc; }
+    if ((rc = d_he_buf.alloc(n_pairs * 8)) || (rc = d_out_buf.alloc(n_pairs * 20))) return rc;
+    int32_t *d_he = d_he_buf.as<int32_t>(), *d_out = d_out_buf.as<int32_t>();
     EventTimer tm;
-    HwTileCounters ctr;
-    auto flag_error = [&](uint32_t flags) -> int {
-        if (flags & HWT_ERR_INDEX) return ISOCON_E_ARG;
-        if (flags & HWT_ERR_K_NEGATIVE) { g_last_error = "isocon_hw_pairs: k must be >= 0 (the band is derived from it)"; return ISOCON_E_ARG; }
-        if (flags & HWT_ERR_K_LARGE) return ISOCON_E_UNSUPPORTED;
-        if (flags & HWT_ERR_BAND) { g_last_error = "isocon_hw_pairs: a pair's band needs more than 512 diagonals (not supported)"; return ISOCON_E_UNSUPPORTED; }
-        if (flags & HWT_ERR_TILE_BAND) { *retry_host = true; return ISOCON_E_UNSUPPORTED; }
-        if (flags & HWT_ERR_STATUS) { g_last_error = "isocon_hw_pairs: internal status from a kernel"; return ISOCON_E_HIP; }
-        return ISOCON_OK;
-    };
-    auto tile_in = [&](int c, const HwTileCounters &cc) {
-        HwTileIn in{};
-        in.tile_q = d_tq.as<uint32_t>(); in.lane_pair = d_lp.as<uint32_t>(); in.pt = d_t; in.pk = d_k;
-        in.n_tiles = cc.cls[c]; in.tile_list = d_cls.as<uint32_t>() + (size_t)c * max_tiles; in.flags = &d_ctr.as<HwTileCounters>()->flags;
-        return in;
-    };
+    HwStageTiles tiles;
     // ---- LOCATE ----
     tm.start();
-    if ((rc = hw_device_tiles<0>(s, n_pairs, d_q, d_t, d_k, d_he.as<int32_t>(), d_out.as<int32_t>(), d_key.as<uint32_t>(),
-                                 d_hist.as<uint32_t>(), d_cursor.as<uint32_t>(), d_tbase.as<uint32_t>(), n_keys, d_tq.as<uint32_t>(), d_lp.as<uint32_t>(), max_tiles,
-                                 d_cls.as<uint32_t>(), d_ctr.as<HwTileCounters>(), ctr)))
-        return rc;
+    if ((rc = drv.build_device<0>(n_pairs, d_q, d_t, d_k, d_he, d_out, tiles))) return rc;
     tm.stop();
-    if ((rc = flag_error(ctr.flags))) return rc;
+    if ((rc = hw_flag_error(tiles.ctr.flags, "isocon_hw_pairs", retry_host))) return rc;
     clk.lap("hw: locate tiles (device)");
     tm.start();
-    for (int c = 0; c < 4; ++c) {
-        g_hw_stats[HS_LOCATE + c] = (double)ctr.cls[c];
-        if (!ctr.cls[c]) continue;
-        const HwTileIn in = tile_in(c, ctr);
-        rc = c == 0 ? hw_launch_locate<1>(s, in, d_he.as<int32_t>()) : c == 1 ? hw_launch_locate<2>(s, in, d_he.as<int32_t>())
-           : c == 2 ? hw_launch_locate<4>(s, in, d_he.as<int32_t>()) : hw_launch_locate<8>(s, in, d_he.as<int32_t>());
-        if (rc) return rc;
-    }
+    if ((rc = drv.for_classes(tiles, d_t, d_k, g_hw_stats + HS_LOCATE, [&](int c, const HwTileIn &in) { return hw_launch_locate(s, c, in, d_he); }))) return rc;
     // ---- START + TRACE + walk for the hits ----
-    if ((rc = hw_device_tiles<1>(s, n_pairs, d_q, d_t, d_k, d_he.as<int32_t>(), d_out.as<int32_t>(), d_key.as<uint32_t>(),
-                                 d_hist.as<uint32_t>(), d_cursor.as<uint32_t>(), d_tbase.as<uint32_t>(), n_keys, d_tq.as<uint32_t>(), d_lp.as<uint32_t>(), max_tiles,
-                                 d_cls.as<uint32_t>(), d_ctr.as<HwTileCounters>(), ctr)))
-        return rc;
+    if ((rc = drv.build_device<1>(n_pairs, d_q, d_t, d_k, d_he, d_out, tiles))) return rc;
     tm.stop();
-    if ((rc = flag_error(ctr.flags))) return rc;
+    if ((rc = hw_flag_error(tiles.ctr.flags, "isocon_hw_pairs", retry_host))) return rc;
     clk.lap("hw: locate kernels + finish tiles (device)");
-    const uint32_t trace_cols = (uint32_t)s->maxlen + 1;
-    for (int c = 0; c < 4; ++c) {
-        g_hw_stats[HS_FINISH + c] = (double)ctr.cls[c];
-        if (!ctr.cls[c]) continue;
-        const int Wc = 1 << c;
-        const HwTileIn in = tile_in(c, ctr);
-        const uint64_t per_block = hw_finish_store_bytes(Wc, trace_cols);
-        size_t free_b = 0, total_b = 0;
-        uint64_t budget = (uint64_t)12 << 30;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = std::min<uint64_t>(budget, (uint64_t)free_b / 3);
-        const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(in.n_tiles, hw_finish_grid_cap(Wc)), budget / per_block));
-        g_hw_stats[HS_GRID + c] = (double)grid;
-        if ((rc = d_trace.alloc((size_t)grid * per_block))) return rc;
-        tm.start();
-        rc = c == 0 ? hw_launch_finish<1>(s, in, grid, d_he.as<int32_t>(), d_trace.as<uint64_t>(), trace_cols, d_out.as<int32_t>())
-           : c == 1 ? hw_launch_finish<2>(s, in, grid, d_he.as<int32_t>(), d_trace.as<uint64_t>(), trace_cols, d_out.as<int32_t>())
-           : c == 2 ? hw_launch_finish<4>(s, in, grid, d_he.as<int32_t>(), d_trace.as<uint64_t>(), trace_cols, d_out.as<int32_t>())
-                    : hw_launch_finish<8>(s, in, grid, d_he.as<int32_t>(), d_trace.as<uint64_t>(), trace_cols, d_out.as<int32_t>());
-        if (rc) return rc;
-        tm.stop();                                  // also the fence before the column store is reused / regrown
-    }
+    if ((rc = drv.finish_stage(tiles, d_t, d_k, d_he, d_out, tm, g_hw_stats))) return rc;
     clk.lap("hw: finish kernels");
-    ISO_HIP_CHECK(hipMemcpy(&ctr, d_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost));
-    if ((rc = flag_error(ctr.flags))) return rc;
-    *d_rows = d_out.as<int32_t>();
+    if ((rc = drv.read_counters(tiles.ctr)) || (rc = hw_flag_error(tiles.ctr.flags, "isocon_hw_pairs", retry_host))) return rc;
+    *d_rows = d_out;
     if (kernel_ms) *kernel_ms = tm.total;
     return ISOCON_OK;
 }

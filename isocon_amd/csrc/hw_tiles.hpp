@@ -15,9 +15,6 @@ static constexpr uint32_t HWT_NONE = 0xffffffffu;
 // counters of one stage, zeroed by the host: [0] error flags, [1] tiles in all, [2..5] tiles per class
 struct HwTileCounters { uint32_t flags, n_tiles, cls[4], pad[2]; };
 
-ISO_HD int hwt_words(int32_t rows) { return rows <= 64 ? 1 : rows <= 128 ? 2 : rows <= 256 ? 4 : rows <= 512 ? 8 : 0; }
-ISO_HD uint32_t hwt_class(int words) { return words == 1 ? 0u : words == 2 ? 1u : words == 4 ? 2u : 3u; }
-
 // one count per distinct key of the wave: lanes holding the same key are counted by their lowest lane.  Returns the lane's rank among the
 // lanes of its key and (in `leader_base`, valid for every lane of the key) the value the counter had before.
 __device__ __forceinline__ uint32_t hwt_wave_add(uint32_t *__restrict__ counters, uint32_t key, uint32_t &leader_base)

@@ -10,6 +10,7 @@
 #include <memory>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "common.hpp"
@@ -27,6 +28,7 @@
 #include "msa.hpp"
 #include "hw.hpp"
 #include "hw_tiles.hpp"
+#include "hw_plan.hpp"
 #include "hw_loc.hpp"
 #include "hw_full.hpp"
 #include "hw_graph.hpp"

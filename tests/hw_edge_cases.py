@@ -43,12 +43,12 @@ def rows(delta, k):
 
 
 def words(r):
-    """window words of a band of r diagonals (csrc/hw_host.inc hw_words), 0: none"""
+    """window words of a band of r diagonals (csrc/hw_core.hpp hwt_words), 0: none"""
     return 1 if r <= 64 else 2 if r <= 128 else 4 if r <= 256 else 8 if r <= 512 else 0
 
 
 def finish_grid_cap(W):
-    """csrc/hw_host.inc hw_finish_grid_cap: the most workgroups a START / TRACE launch gets"""
+    """csrc/hw_plan.hpp hw_finish_grid_cap: the most workgroups a START / TRACE launch gets"""
     lds = HW_SEG * 2 * W * 64 * 8 if W == 2 else 0
     return 256 * (160 * 1024 // (lds + 256)) if W == 2 else 4096
 
@@ -402,7 +402,7 @@ def flatten(case_list, bystander=None):
 
 
 def host_tiles(case):
-    """The LOCATE tiles the host's greedy cut forms for the pairs of one query (csrc/hw_host.inc hw_build_tiles, restated): a list of
+    """The LOCATE tiles the host's greedy cut forms for the pairs of one query (csrc/hw_plan.hpp hw_build_tiles with HwLocateCut, restated): a list of
     (W, [lanes]).  Pairs that need no kernel are in no tile."""
     P = len(case.query)
     need = [i for i, (t, k) in enumerate(zip(case.targets, case.ks)) if len(t) - P >= -k and P and len(t)]
