@@ -589,6 +589,47 @@ int isocon_hw_locations(isocon_store *s, const uint32_t *q, const uint32_t *t, c
 int isocon_hw_locations_last_stats(double *out, int32_t cap);
 
 /*
+ * Prefix alignments of a pair list: edlib.align(q, t, mode="SHW", k) -- the whole query against a PREFIX of the target (a primer that
+ * must sit at the read's start; on reversed strings, at its end).  With D the global matrix of query q[p] (length P) and target t[p]
+ * (length n) -- D[0][j] = j, D[i][0] = i -- h = min over columns 1 <= j <= n of D[P][j] = min over j of ed(q, t[0..j)): out_ed[p] = h if
+ * h <= k[p], else -1.  A hit owns the ends out_ends[out_end_ptr[p] .. out_end_ptr[p + 1]): every 0-based column end = j - 1 with
+ * D[P][j] == h, ascending; they lie in [P - h - 1, P + h - 1], at most 2 h + 1 of them, and edlib's `locations` are (0, end) for each.
+ * A miss (above k[p], an empty sequence, n - P < -k[p]) owns none.  k[p] >= 0 is required (ISOCON_E_ARG, as an id out of range); a
+ * threshold above len(q) asks no more than len(q) (h <= P) and is taken as that.  A store of more than four symbols returns
+ * ISOCON_E_ALPHABET.  ISOCON_E_CAPACITY + *needed when the ends exceed cap (out_ed and out_end_ptr are valid then).  At most 2^32 - 16
+ * pairs and ends per call.
+ * All stages run on the device, on a band of 2 thr + 1 diagonals whatever the target's length is (only its first P + thr columns are
+ * read).  The distance stage runs in up to four rounds of thresholds min(k[p], 31), 63, 127, 255 -- windows of 1, 2, 4, 8 words --; a
+ * pair leaves them when it hits or has missed at its own threshold, so an unbounded search costs what its distance needs.  A pair
+ * that no round settles (k[p] > 255 and h > 255; never a query of at most 255 bases) fails the call with ISOCON_E_UNSUPPORTED, and
+ * isocon_last_error names the first such pair: there is no un-banded prefix pass.  The ends come from the same recurrence on the hits
+ * with threshold h, run twice (count, then fill).  *kernel_ms sums the stages.
+ */
+int isocon_shw_locations(isocon_store *s, const uint32_t *q, const uint32_t *t, const int32_t *k, uint64_t n_pairs,
+                         int32_t *out_ed /* n_pairs */, uint64_t *out_end_ptr /* n_pairs + 1 */, int32_t *out_ends /* cap */,
+                         uint64_t cap, uint64_t *needed, float *kernel_ms);
+
+/*
+ * edlib.align(q, t, mode="SHW", task="path", k) for a pair list.  out (n_pairs, 2) = (distance or -1, first end or -1) of
+ * isocon_shw_locations for the same arguments, with that entry's checks, statuses and rounds.  A hit owns
+ * out_ops[out_ops_ptr[p] .. out_ops_ptr[p + 1]), ops as in isocon_ed_path_pairs: the global alignment of the query against
+ * t[0 .. end] for the FIRST end, under the tie rule used everywhere else (from the end cell: 'I', then 'D', then the diagonal); a miss
+ * has no ops.  ISOCON_E_CAPACITY + *needed when ops_cap is too small (out and out_ops_ptr are valid then).  The paths come from the
+ * trace kernels of isocon_ed_path_pairs over the window of end + 1 columns (isocon_path_last_stats tells their classes).
+ */
+int isocon_shw_path_pairs(isocon_store *s, const uint32_t *q, const uint32_t *t, const int32_t *k, uint64_t n_pairs,
+                          int32_t *out /* n_pairs x 2 */, uint32_t *out_ops, uint64_t *out_ops_ptr, uint64_t ops_cap,
+                          uint64_t *needed, float *kernel_ms);
+
+/*
+ * What the calling thread's last isocon_shw_locations / isocon_shw_path_pairs call did (no counterpart in the reference; tests and
+ * timing scripts): out[0] pairs, out[1] hits, out[2] ends (locations entry only), out[3] rounds of the distance stage that ran,
+ * out[4..7] pairs entering round 0 .. 3, out[8..11] tiles of the distance stage per class of 1, 2, 4, 8 window words summed over the
+ * rounds, out[12..15] tiles of an ends run per class.  Writes min(cap, 16) values and returns that number.
+ */
+int isocon_shw_last_stats(double *out, int32_t cap);
+
+/*
  * How the calling thread's last isocon_ed_path_pairs / isocon_hw_path_pairs call traced its hits (no counterpart in the reference).
  * out[0] hits traced; out[1..3] hits of the banded classes of 1, 2 and 4 window words (64, 128, 256 diagonals); out[4] hits of the
  * un-banded kernel; out[5] / out[6] bytes of trace banded / un-banded; out[7] / out[8] launches banded / un-banded; out[9] / out[10]

@@ -21,12 +21,24 @@
 
 namespace isocon {
 
-enum { HW_LOCATE = 0, HW_START = 1, HW_TRACE = 2, HW_TRACE_CK = 3, HW_ENDS = 4 };
+enum { HW_LOCATE = 0, HW_START = 1, HW_TRACE = 2, HW_TRACE_CK = 3, HW_ENDS = 4, HW_PREFIX_LOCATE = 5, HW_PREFIX_ENDS = 6 };
 // HW_TRACE_CK: the TRACE pass that keeps only CHECKPOINTS -- the band state (VP, VN) after every HW_SEG-th column -- instead of every
 // column's VP / HP: the walk then goes segment by segment from the end, each segment's columns recomputed from its checkpoint
 // (hw_trace_segment) into a small buffer (LDS on the device) and walked there (hw_walk_segment).  1 byte per column and word instead of 16.
 // HW_ENDS: the LOCATE recurrence run again on a hit with its distance as the threshold (ln.k = ln.h = h): every column whose last-row value
 // equals h goes to the sink, in ascending order -- all the end positions edlib reports for the pair, not only the first.
+// HW_PREFIX_LOCATE / HW_PREFIX_ENDS: the prefix ("SHW") question -- the whole query against a prefix of the target, what edlib.align(q, t,
+// mode="SHW") answers.  The recurrence of START (row 0 = j, diagonals [-kmax, kmax]: a0 = -kmax) on FORWARD streams, collected like LOCATE
+// and ENDS: h = the minimum of the last row over the columns j in [P - k, min(n, P + k)] (ln.ncols = min(n, P + k): a prefix longer than
+// P + k costs more than k), r_end the first column attaining it; PREFIX_ENDS sinks every column whose last-row value equals ln.h = ln.k.
+// Abandoning a lane under a GLOBAL top row: the band recurrence holds, for every cell of the window, the cost of the cheapest alignment
+// of the query's first i bases with the target's first j that stays inside the window (the steps it leaves out come from outside it), so
+// each value is at most the cost of any such path.  An alignment of the query with a LATER prefix t[0..j') of cost <= k starts on
+// diagonal 0 and therefore stays on the diagonals [-k, k], inside the window [-kmax, kmax]; it crosses the current column in a window
+// cell whose value is then <= k.  top - popcount(VN) is a lower bound of every value of the column (every downward step is >= -1 and
+// is -1 only where VN is set, the rows below the query included), so once it exceeds k no later column can hold a value <= k, and the
+// columns already read keep what they gave.  (Unlike the zero top row there is no virtual row of D = 0 to wait for: row 0 = j grows
+// with the column, which is what makes the exit fire early on a target that drifts off the query.)
 static constexpr int HW_SEG = 8;
 static constexpr int32_t HWB_INF = 1 << 28;
 
@@ -38,8 +50,8 @@ struct HwTile {          // wave-uniform
 };
 
 struct HwLane {
-    int32_t ncols;       // columns of this lane (LOCATE: len(target); START: min(end + 1, P + kmax); TRACE: end - start + 1); 0 = empty lane
-    int32_t k;           // LOCATE: threshold of the pair
+    int32_t ncols;       // columns of this lane (LOCATE: len(target); START: min(end + 1, P + kmax); TRACE: end - start + 1; PREFIX_*: min(len(target), P + k)); 0 = empty lane
+    int32_t k;           // LOCATE / PREFIX_LOCATE: threshold of the pair
     int32_t h;           // START / TRACE: the pair's distance
     int32_t r_h, r_end;  // LOCATE: min over columns of D[P][j] (HWB_INF if the lane was abandoned first), 0-based first column attaining it
     int32_t r_pl;        // START: last column j (1-based) with D[P][j] == h, -1 if none
@@ -114,13 +126,14 @@ ISO_HD uint32_t hw_bit(const uint64_t (&V)[W], int32_t r)
 // any_live(live): does any lane of the wave still need columns (device: a ballot; emulator: the lane itself);
 // sink(j, word, vp_new, hp): TRACE; sink(j / HW_SEG, word, vp_new, vn_new) after every column j that is a multiple of HW_SEG: TRACE_CK
 // (there T.jx = the smallest ncols of the tile's lanes: the blocks before it take the unrolled path); sink(end, 0, 0, 0) for every
-// 0-based column `end` whose last-row value equals ln.h: ENDS.  ENDS abandons a lane by LOCATE's rule with ln.k = h, which stays sound
+// 0-based column `end` whose last-row value equals ln.h: ENDS and PREFIX_ENDS.  ENDS abandons a lane by LOCATE's rule with ln.k = h, which stays sound
 // for the later ends: while a later occurrence can still start at or behind the current column the window's top row is a virtual row
 // (D = 0), so the bound is <= 0; afterwards every alignment of cost <= h that ends in a later column crosses this column inside the band.
 template <int W, int MODE, class PLo, class PHi, class Text, class AnyLive, class Sink>
 ISO_HD void hw_run(const HwTile &T, HwLane &ln, PLo plo, PHi phi, Text text, AnyLive any_live, Sink sink)
 {
     constexpr bool ZT = MODE == HW_LOCATE || MODE == HW_ENDS;
+    constexpr bool PFX = MODE == HW_PREFIX_LOCATE || MODE == HW_PREFIX_ENDS;
     const int32_t nv = -T.a0;
     BandLane<W> L;
     uint64_t NL[W], NH[W], VM[W], FL = 0, FH = 0;
@@ -185,12 +198,12 @@ ISO_HD void hw_run(const HwTile &T, HwLane &ln, PLo plo, PHi phi, Text text, Any
                 const int32_t j = jb + jj + 1;
                 const int32_t top = top0 + j - (int32_t)L.ztop;
                 const int32_t b = T.P - T.a0 - j;              // window bit of the last row in this column
-                if (MODE == HW_LOCATE) {
+                if (MODE == HW_LOCATE || MODE == HW_PREFIX_LOCATE) {
                     if (live && j >= T.P - ln.k && j <= ln.ncols && b >= 0 && b < 64 * W) {
                         const int32_t v = hw_row_value<W>(L, top, b);
                         if (v < h) { h = v; end = j - 1; }
                     }
-                } else if (MODE == HW_ENDS) {
+                } else if (MODE == HW_ENDS || MODE == HW_PREFIX_ENDS) {
                     if (live && j >= T.P - ln.k && j <= ln.ncols && b >= 0 && b < 64 * W) {
                         if (hw_row_value<W>(L, top, b) == ln.h) sink(j - 1, 0, 0, 0);
                     }
@@ -219,7 +232,7 @@ ISO_HD void hw_run(const HwTile &T, HwLane &ln, PLo plo, PHi phi, Text text, Any
                 }
             }
         }
-        if (ZT) {
+        if (ZT || PFX) {
             if (live) {
                 const int32_t cols = jb + cnt;
                 if (cols >= ln.ncols) live = false;

@@ -1,5 +1,5 @@
-// hw_plan.hpp -- what the host decides for the banded infix kernels (hw.hpp, hw_loc.hpp) without a device: the greedy cut of a pair list
-// into tiles of one query x up to 64 targets, its two cut rules, and the LDS, column store and grid of k_hw_finish.  Plain C++ (no HIP):
+// hw_plan.hpp -- what the host decides for the banded infix and prefix kernels (hw.hpp, hw_loc.hpp, shw.hpp) without a device: the greedy cut
+// of a pair list into tiles of one query x up to 64 targets, its cut rules, and the LDS, column store and grid of k_hw_finish.  Plain C++ (no HIP):
 // hw_host.inc runs it, tests/emul/hw_plan_emul.cpp drives it on its own (tests/test_hw_plan.py, also with -fsanitize=address,undefined).
 #pragma once
 #include <algorithm>
@@ -36,6 +36,17 @@ struct HwFinishCut {          // 2 k + 1 diagonals: START + TRACE of the hits
     bool fits(uint32_t p, int32_t &dmax, int32_t &kmax, int W) const
     {
         const int32_t k2 = std::max(kmax, k[p]);
+        if (2 * k2 + 1 > 64 * W) return false;
+        dmax = 0; kmax = k2;
+        return true;
+    }
+};
+struct HwPrefixCut {          // 2 thr + 1 diagonals: the prefix passes (shw.hpp), thr = the round's threshold or the pair's distance
+    const int32_t *thr;
+    int words(uint32_t p) const { return thr[p] <= 255 ? hwt_words(2 * thr[p] + 1) : 0; }
+    bool fits(uint32_t p, int32_t &dmax, int32_t &kmax, int W) const
+    {
+        const int32_t k2 = std::max(kmax, thr[p]);          // (the class of the largest threshold: joining a tile never widens it)
         if (2 * k2 + 1 > 64 * W) return false;
         dmax = 0; kmax = k2;
         return true;

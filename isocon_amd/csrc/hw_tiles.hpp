@@ -39,6 +39,11 @@ __device__ __forceinline__ uint32_t hwt_wave_add(uint32_t *__restrict__ counters
 // STAGE 0 (LOCATE): every pair that needs a kernel gets key = 4 query + class of its own band; the others (distance > k by the lengths
 // alone, an empty sequence) none; out5 / he get their "no hit" rows.  STAGE 1 (START + TRACE): the hits of he.  STAGE 2 (ENDS of
 // isocon_hw_locations): k[p] = the pair's distance or -1, the hits keyed by the LOCATE band of that distance; he / out5 are not touched.
+// STAGE 3 (prefix alignments, shw.hpp): k[p] = the pair's threshold of this run or HWT_SKIP (the pair takes no part: settled in an earlier
+// round, no hit); a pair that needs a kernel -- neither sequence empty, len(t) - len(q) >= -k[p] -- is keyed by the class of its
+// 2 k[p] + 1 diagonals, so a tile's class follows from its largest threshold alone and a tile never outgrows its class.  Ids and
+// negative thresholds are flagged as in STAGE 0; he / out5 are not touched.
+static constexpr int32_t HWT_SKIP = -(1 << 30);
 template <int STAGE>
 __global__ __launch_bounds__(256) void k_hwt_keys(DevStore S, const uint32_t *__restrict__ q, const uint32_t *__restrict__ t, const int32_t *__restrict__ k,
                                                    unsigned long long n_pairs, int32_t *__restrict__ he, int32_t *__restrict__ out5, uint32_t *__restrict__ key,
@@ -66,6 +71,20 @@ __global__ __launch_bounds__(256) void k_hwt_keys(DevStore S, const uint32_t *__
             he[p * 2] = -1; he[p * 2 + 1] = -1;
             int32_t *o = out5 + p * 5;
             o[0] = -1; o[1] = -1; o[2] = -1; o[3] = 0; o[4] = 0;
+        } else if (STAGE == 3) {
+            uint32_t err = 0;
+            if (qq >= S.n || tt >= S.n) err = HWT_ERR_INDEX;
+            else if (kv == HWT_SKIP) err = 0;
+            else if (kv < 0) err = HWT_ERR_K_NEGATIVE;
+            else {
+                const int32_t lq = S.lens[qq], lt = S.lens[tt];
+                if (!(lt - lq < -kv || lq == 0 || lt == 0)) {
+                    const int w = kv <= 255 ? hwt_words(2 * kv + 1) : 0;
+                    if (!w) err = HWT_ERR_BAND;
+                    else kk = qq * 4u + hwt_class(w);
+                }
+            }
+            if (err) atomicOr(&ctr->flags, err);
         } else if (STAGE == 2) {
             if (kv < -1) atomicOr(&ctr->flags, (uint32_t)HWT_ERR_STATUS);
             else if (kv >= 0) {
@@ -115,7 +134,7 @@ __global__ __launch_bounds__(256) void k_hwt_classes(DevStore S, const uint32_t 
     const int32_t kv = has ? k[pair] : 0;
     const int32_t delta = has ? S.lens[t[pair]] - P : -(1 << 30);
     const int32_t dmax = wave_max_i32(delta), kmax = wave_max_i32(kv);
-    const int w = hwt_words(STAGE != 1 ? hw_locate_rows(dmax, kmax) : 2 * kmax + 1);
+    const int w = hwt_words(STAGE == 0 || STAGE == 2 ? hw_locate_rows(dmax, kmax) : 2 * kmax + 1);
     if (lane == 0) {
         if (!w) atomicOr(&ctr->flags, (uint32_t)HWT_ERR_TILE_BAND);
         else {

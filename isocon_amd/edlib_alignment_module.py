@@ -113,6 +113,8 @@ TRACEBACK_STATS = {"device": 0, "host": 0}
 TRACEBACK_INFIX_STATS = {"device": 0}
 # the calls of edlib_traceback_infix_all (isocon_hw_locations + isocon_hw_path_pairs; the device route alone)
 TRACEBACK_INFIX_ALL_STATS = {"device": 0}
+# the calls of edlib_traceback_prefix (isocon_shw_locations + isocon_shw_path_pairs; the device route alone)
+TRACEBACK_PREFIX_STATS = {"device": 0}
 
 
 def _cigar_of_steps(steps):
@@ -206,3 +208,24 @@ def edlib_traceback_infix_all(x, y, k=1):
     if ed[0] < 0:
         return -1, [], None
     return int(ed[0]), [(int(s), int(e)) for s, e in locs[int(loc_ptr[0]):int(loc_ptr[1])].tolist()], "".join("%d%s" % (o >> 4, "=XID"[o & 15]) for o in ops.tolist())
+
+
+def edlib_traceback_prefix(x, y, k=1):
+    """(editDistance, locations, cigar) of edlib.align(x, y, mode="SHW", task="path", k=k): the whole of x against a PREFIX of y -- what a
+    primer or barcode search asks when the primer must sit at the read's start (on reversed strings: at its end).  editDistance is
+    min over j of ed(x, y[:j]); locations holds (0, end) for every end that attains it, in ascending order (SeqStore.shw_locations);
+    the cigar is the global alignment of x against y[:end + 1] for the first of them, under the tie rule used everywhere else (from the
+    end: I, then D, then the diagonal; SeqStore.shw_path_pairs).  k None or negative: unbounded.  Above k, and for an empty x or y:
+    (-1, [], None).  GPU only and at most four distinct symbols, like edlib_traceback_infix; a pair above distance 255 under a
+    threshold beyond it raises IsoconError.  edlib_traceback(mode="SHW") keeps raising NotImplementedError."""
+    kk = None if k is None or k < 0 else [int(k)]
+    st = SeqStore([x, y])
+    try:
+        ed, end_ptr, ends = st.shw_locations([0], [1], kk)
+        ops = st.shw_path_pairs([0], [1], kk)[1] if ed[0] >= 0 else None
+    finally:
+        st.close()
+    TRACEBACK_PREFIX_STATS["device"] += 1
+    if ed[0] < 0:
+        return -1, [], None
+    return int(ed[0]), [(0, int(e)) for e in ends[int(end_ptr[0]):int(end_ptr[1])].tolist()], "".join("%d%s" % (o >> 4, "=XID"[o & 15]) for o in ops.tolist())

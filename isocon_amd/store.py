@@ -201,6 +201,63 @@ class SeqStore(object):
             out = (ed, loc_ptr, locs[:int(loc_ptr[n])])
             return out + (ms.value,) if return_ms else out
 
+    def _shw_args(self, q, t, k):
+        q = np.ascontiguousarray(q, dtype=np.uint32)
+        t = np.ascontiguousarray(t, dtype=np.uint32)
+        if len(q) != len(t):
+            raise ValueError("pair arrays differ in length")
+        # (an id out of range is the library's to refuse)
+        qlen = np.take(np.asarray(self.lens, dtype=np.int64), q, mode="clip") if self.n else np.zeros(len(q), dtype=np.int64)
+        kk = np.broadcast_to(np.asarray(-1 if k is None else k, dtype=np.int64), q.shape)
+        return q, t, np.ascontiguousarray(np.where(kk < 0, qlen, kk).clip(max=2 ** 31 - 1), dtype=np.int32)
+
+    def shw_locations(self, q, t, k=None, return_ms=False):
+        """Prefix alignments, edlib.align(q[p], t[p], mode="SHW", k[p]) for a pair list (isocon_shw_locations): the whole of q[p] against a
+        prefix of t[p].  (ed int32[n] -- h = min over j of ed(q, t[:j]), or -1 above k --, end_ptr uint64[n + 1], ends int32[L]); a hit p
+        owns ends[end_ptr[p]:end_ptr[p + 1]], every 0-based end with ed(q, t[:end + 1]) == h in ascending order (edlib's locations are
+        (0, end)).  k: a scalar or one value per pair; None or a negative value: unbounded (sent as len(q[p]), which h never exceeds).
+        At most four symbols; a pair above distance 255 under a threshold beyond it is refused (IsoconError, ISOCON_E_UNSUPPORTED) --
+        never a query of at most 255 bases.  shw_last_stats() tells the rounds of the last call."""
+        q, t, kk = self._shw_args(q, t, k)
+        n = len(q)
+        ed = np.full(n, -1, dtype=np.int32)
+        end_ptr = np.zeros(n + 1, dtype=np.uint64)
+        cap = 4 * n + 1024
+        needed = ctypes.c_uint64(0)
+        ms = ctypes.c_float(0)
+        while True:
+            ends = np.empty(cap, dtype=np.int32)
+            rc = self._L.isocon_shw_locations(self._h, _ptr(q, _lib.u32p), _ptr(t, _lib.u32p), _ptr(kk, _lib.i32p), n, _ptr(ed, _lib.i32p),
+                                              _ptr(end_ptr, _lib.u64p), _ptr(ends, _lib.i32p), cap, ctypes.byref(needed), ctypes.byref(ms))
+            if rc == _lib.ISOCON_E_CAPACITY:
+                cap = int(needed.value) + 16
+                continue
+            _lib.check(rc, "isocon_shw_locations")
+            out = (ed, end_ptr, ends[:int(end_ptr[n])])
+            return out + (ms.value,) if return_ms else out
+
+    def shw_path_pairs(self, q, t, k=None, return_ms=False):
+        """edlib.align(q[p], t[p], mode="SHW", task="path", k[p]) for a pair list (isocon_shw_path_pairs): (rows int32[n, 2] -- distance or
+        -1, first end or -1 --, ops uint32[], ops_ptr uint64[n + 1]); a hit p owns ops[ops_ptr[p]:ops_ptr[p + 1]], the global alignment of
+        q[p] against t[p][:end + 1], encoded as in ed_path_pairs.  k and the limits as in shw_locations."""
+        q, t, kk = self._shw_args(q, t, k)
+        n = len(q)
+        rows = np.full((n, 2), -1, dtype=np.int32)
+        ops_ptr = np.zeros(n + 1, dtype=np.uint64)
+        cap = min(256 * n, 1 << 26) + 1024     # (as ed_path_pairs)
+        needed = ctypes.c_uint64(0)
+        ms = ctypes.c_float(0)
+        while True:
+            ops = np.empty(cap, dtype=np.uint32)
+            rc = self._L.isocon_shw_path_pairs(self._h, _ptr(q, _lib.u32p), _ptr(t, _lib.u32p), _ptr(kk, _lib.i32p), n, _ptr(rows, _lib.i32p),
+                                               _ptr(ops, _lib.u32p), _ptr(ops_ptr, _lib.u64p), cap, ctypes.byref(needed), ctypes.byref(ms))
+            if rc == _lib.ISOCON_E_CAPACITY:
+                cap = int(needed.value) + 16
+                continue
+            _lib.check(rc, "isocon_shw_path_pairs")
+            out = (rows, ops[:int(ops_ptr[n])], ops_ptr)
+            return out + (ms.value,) if return_ms else out
+
     def qgram_bound_pairs(self, a, b):
         """Lower bounds of ed(a[i], b[i]) from q-gram count profiles (csrc/qgram_mm.hpp) -- the pre-filter of the NN main pass."""
         a = np.ascontiguousarray(a, dtype=np.uint32)
@@ -713,6 +770,17 @@ def hw_locations_last_stats():
     _lib.load().isocon_hw_locations_last_stats(out, 16)
     keys = ("pairs", "hits", "locations", "host_cuts") + tuple(
         "%s_w%d" % (name, w) for name in ("locate_tiles", "ends_tiles", "starts_tiles") for w in (1, 2, 4, 8))
+    return {key: int(v) for key, v in zip(keys, out)}
+
+
+def shw_last_stats():
+    """what this thread's most recent shw_locations / shw_path_pairs call did (isocon_shw_last_stats, include/isocon_hip.h): pairs, hits,
+    ends, rounds of the distance stage, pairs entering each round, and per class of 1, 2, 4, 8 window words the tiles of the distance
+    stage (summed over the rounds) and of an ends run"""
+    out = (ctypes.c_double * 16)()
+    _lib.load().isocon_shw_last_stats(out, 16)
+    keys = ("pairs", "hits", "ends", "rounds") + tuple("enter_round%d" % r for r in range(4)) + tuple(
+        "%s_w%d" % (name, w) for name in ("locate_tiles", "ends_tiles") for w in (1, 2, 4, 8))
     return {key: int(v) for key, v in zip(keys, out)}
 
 
