@@ -3,11 +3,6 @@
 
 namespace {
 
-// Trace scratch one launch of k_hwf_finish may hold (SLOT_HW_TRACE): the host cuts the hits into as many launches as that takes, a
-// pair whose own store exceeds it is refused.  ISOCON_DEBUG_VARIANT=hw_trace_budget=<bytes> (tests: many launches at small shapes).
-static constexpr uint64_t kHwfTraceBudget = (uint64_t)1 << 30;
-static constexpr size_t kHwfMaxLds = (size_t)160 << 10;
-
 // does isocon_hw_pairs take the pair (it needs no kernel, or its band fits)?
 inline bool hwf_is_narrow(int32_t len_q, int32_t len_t, int32_t kk)
 {
@@ -52,7 +47,8 @@ int hwf_pairs(isocon_store *s, const std::vector<uint32_t> &q, const std::vector
     clk.lap("hw wide: locate");
     std::vector<int32_t> he(nw * 2);
     ISO_HIP_CHECK(copy_d2h(he.data(), d_he.p, nw * 8));
-    // ---- START + TRACE + walk for the hits, in launches whose trace stores fit the budget ----
+    // ---- START + TRACE + walk for the hits, in launches whose trace stores fit the budget (kHwfTraceBudget and the cut: nwp_plan.hpp; a
+    //      pair whose own store exceeds it is refused).  ISOCON_DEBUG_VARIANT=hw_trace_budget=<bytes> (tests: many launches at small shapes) ----
     uint64_t budget = kHwfTraceBudget;
     if (const char *e = variant_value("hw_trace_budget")) budget = strtoull(e, nullptr, 10);
     std::vector<uint32_t> hits;
@@ -70,25 +66,22 @@ int hwf_pairs(isocon_store *s, const std::vector<uint32_t> &q, const std::vector
         hits.push_back((uint32_t)x);
         units.push_back(u);
     }
-    size_t launches = 0;
-    for (size_t a = 0; a < hits.size();) {
-        std::vector<uint64_t> off;
-        uint64_t total = 0;
-        size_t b = a;
-        while (b < hits.size() && (total + units[b]) * 16 <= budget && b - a < ((size_t)1 << 20)) { off.push_back(total); total += units[b]; ++b; }
-        const size_t cnt = b - a;
-        if ((rc = d_list.alloc(cnt * 4)) || (rc = d_off.alloc(cnt * 8)) || (rc = d_trace.alloc((size_t)total * 16))) return rc;
-        ISO_HIP_CHECK(copy_h2d(d_list.p, hits.data() + a, cnt * 4));
-        ISO_HIP_CHECK(copy_h2d(d_off.p, off.data(), cnt * 8));
-        in.list = d_list.as<uint32_t>(); in.trace_off = d_off.as<uint64_t>(); in.n = (uint32_t)cnt;
+    // (the list and the offsets go up once, the store is that of the largest launch, as in nwp_paths)
+    const BudgetCut cut = budget_cut(units.data(), units.size(), budget);
+    if (!hits.empty()) {
+        if ((rc = d_list.alloc(hits.size() * 4)) || (rc = d_off.alloc(hits.size() * 8)) || (rc = d_trace.alloc((size_t)cut.most * 16))) return rc;
+        ISO_HIP_CHECK(copy_h2d(d_list.p, hits.data(), hits.size() * 4));
+        ISO_HIP_CHECK(copy_h2d(d_off.p, cut.off.data(), hits.size() * 8));
+    }
+    for (size_t c = 0; c + 1 < cut.cut.size(); ++c) {
+        const size_t a = cut.cut[c], cnt = cut.cut[c + 1] - a;
+        in.list = d_list.as<uint32_t>() + a; in.trace_off = d_off.as<uint64_t>() + a; in.n = (uint32_t)cnt;
         tm.start();
         hipLaunchKernelGGL(k_hwf_finish, dim3((unsigned)cnt), dim3(64), lds, 0, s->dev, in, d_he.as<int32_t>(), d_trace.as<ulonglong2>(), d_out.as<int32_t>());
         ISO_HIP_CHECK(hipGetLastError());
-        tm.stop();                                      // also the fence before the list, the offsets and the store are reused
-        ++launches;
-        a = b;
+        tm.stop();                                      // also the fence before the next launch reuses the store
     }
-    if (clk.on) fprintf(stderr, "[isocon] hw wide: %zu pairs, %zu hits, %zu finish launches\n", nw, hits.size(), launches);
+    if (clk.on) fprintf(stderr, "[isocon] hw wide: %zu pairs, %zu hits, %zu finish launches\n", nw, hits.size(), cut.launches());
     clk.lap("hw wide: finish");
     std::vector<int32_t> res;
     if (!hits.empty()) {

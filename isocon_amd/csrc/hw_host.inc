@@ -321,13 +321,7 @@ int hw_pairs_device_tiles(isocon_store *s, const uint32_t *q, const uint32_t *t,
 
 }  // namespace
 
-extern "C" int isocon_hw_last_stats(double *out, int32_t cap)
-{
-    if (!out || cap < 0) return 0;
-    const int k = cap < (int)HS_COUNT ? cap : (int)HS_COUNT;
-    for (int i = 0; i < k; ++i) out[i] = g_hw_stats[i];
-    return k;
-}
+extern "C" int isocon_hw_last_stats(double *out, int32_t cap) { return copy_last_stats(g_hw_stats, HS_COUNT, out, cap); }
 
 extern "C" int isocon_hw_pairs(isocon_store *s, const uint32_t *q, const uint32_t *t, const int32_t *k, uint64_t n_pairs,
                                int32_t *out, float *kernel_ms)

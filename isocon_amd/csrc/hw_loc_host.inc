@@ -32,13 +32,7 @@ int hw_launch_starts(isocon_store *st, int c, const HwTileIn &in, const int32_t 
 
 }  // namespace
 
-extern "C" int isocon_hw_locations_last_stats(double *out, int32_t cap)
-{
-    if (!out || cap < 0) return 0;
-    const int k = cap < (int)HL_COUNT ? cap : (int)HL_COUNT;
-    for (int i = 0; i < k; ++i) out[i] = g_hw_loc_stats[i];
-    return k;
-}
+extern "C" int isocon_hw_locations_last_stats(double *out, int32_t cap) { return copy_last_stats(g_hw_loc_stats, HL_COUNT, out, cap); }
 
 extern "C" int isocon_hw_locations(isocon_store *s, const uint32_t *q, const uint32_t *t, const int32_t *k, uint64_t n_pairs, int32_t *out_ed,
                                    uint64_t *out_loc_ptr, int32_t *out_locs, uint64_t cap, uint64_t *needed, float *kernel_ms)

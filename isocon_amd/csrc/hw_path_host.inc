@@ -5,16 +5,11 @@
 extern "C" int isocon_hw_path_pairs(isocon_store *s, const uint32_t *q, const uint32_t *t, const int32_t *k, uint64_t n_pairs,
                                     int32_t *out, uint32_t *out_ops, uint64_t *out_ops_ptr, uint64_t ops_cap, uint64_t *needed, float *kernel_ms)
 {
-    path_stats_reset();
-    if (!s || !out_ops_ptr || (n_pairs && (!q || !t || !k || !out)) || (ops_cap && !out_ops)) return ISOCON_E_ARG;
-    if (kernel_ms) *kernel_ms = 0.f;
-    if (needed) *needed = 0;
-    out_ops_ptr[0] = 0;
-    if (!n_pairs) return ISOCON_OK;
+    int rc;
+    if (path_prologue(s, n_pairs, {q, t, k, out}, out_ops, out_ops_ptr, ops_cap, needed, kernel_ms, &rc)) return rc;
     HostClock clk;
     // ---- rows: distance, location and terminal insertion runs; the argument checks are that entry's ----
     float ms_rows = 0.f;
-    int rc;
     if ((rc = isocon_hw_pairs_wide(s, q, t, k, n_pairs, out, &ms_rows))) return rc;
     clk.lap("hw path: rows");
     // ---- the hits and their windows, then what both path entries share ----

@@ -29,6 +29,7 @@
 #include "hw.hpp"
 #include "hw_tiles.hpp"
 #include "hw_plan.hpp"
+#include "nwp_plan.hpp"
 #include "hw_loc.hpp"
 #include "shw.hpp"
 #include "hw_full.hpp"
@@ -1084,6 +1085,15 @@ extern "C" int isocon_block_filter_chunks(isocon_store *s, const int32_t *thr, u
         ISO_HIP_CHECK(copy_d2h(out_pb, d_pb.p, (size_t)tot.n_small * 4));
     }
     return ISOCON_OK;
+}
+
+// Every isocon_*_last_stats: the first min(cap, count) statistics of the calling thread's last call into out; how many were written.
+static int copy_last_stats(const double *stats, int count, double *out, int32_t cap)
+{
+    if (!out || cap < 0) return 0;
+    const int k = cap < count ? cap : count;
+    for (int i = 0; i < k; ++i) out[i] = stats[i];
+    return k;
 }
 
 #include "nn_context.inc"

@@ -422,13 +422,7 @@ extern "C" int isocon_sg_strings_batch(isocon_store *s, const uint32_t *a, const
                          n_ops_needed, out_res, kernel_ms, out_aln_a, out_aln_b, out_aln_ptr, aln_cap, n_aln_needed, ed_upper);
 }
 
-extern "C" int isocon_sg_last_stats(double *out, int32_t cap)
-{
-    if (!out || cap < 0) return 0;
-    const int k = cap < 11 ? cap : 11;
-    for (int i = 0; i < k; ++i) out[i] = g_sg_stats[i];
-    return k;
-}
+extern "C" int isocon_sg_last_stats(double *out, int32_t cap) { return copy_last_stats(g_sg_stats, 11, out, cap); }
 
 // functions.filter_exon_differences (/root/reference/modules/functions.py:23-50 with get_mask_start_and_end :218-236)
 // evaluated on CIGAR ops instead of on the gapped strings: flag[p] = 1 iff one of the two gapped strings has a run of

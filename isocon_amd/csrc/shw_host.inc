@@ -119,13 +119,7 @@ int shw_check(isocon_store *s, uint64_t n_pairs)
 
 }  // namespace
 
-extern "C" int isocon_shw_last_stats(double *out, int32_t cap)
-{
-    if (!out || cap < 0) return 0;
-    const int k = cap < (int)SW_COUNT ? cap : (int)SW_COUNT;
-    for (int i = 0; i < k; ++i) out[i] = g_shw_stats[i];
-    return k;
-}
+extern "C" int isocon_shw_last_stats(double *out, int32_t cap) { return copy_last_stats(g_shw_stats, SW_COUNT, out, cap); }
 
 extern "C" int isocon_shw_locations(isocon_store *s, const uint32_t *q, const uint32_t *t, const int32_t *k, uint64_t n_pairs, int32_t *out_ed,
                                     uint64_t *out_end_ptr, int32_t *out_ends, uint64_t cap, uint64_t *needed, float *kernel_ms)
@@ -189,13 +183,8 @@ extern "C" int isocon_shw_path_pairs(isocon_store *s, const uint32_t *q, const u
                                      uint32_t *out_ops, uint64_t *out_ops_ptr, uint64_t ops_cap, uint64_t *needed, float *kernel_ms)
 {
     for (double &x : g_shw_stats) x = 0;
-    path_stats_reset();
-    if (!s || !out_ops_ptr || (n_pairs && (!q || !t || !k || !out)) || (ops_cap && !out_ops)) return ISOCON_E_ARG;
-    if (kernel_ms) *kernel_ms = 0.f;
-    if (needed) *needed = 0;
-    out_ops_ptr[0] = 0;
-    if (!n_pairs) return ISOCON_OK;
     int rc;
+    if (path_prologue(s, n_pairs, {q, t, k, out}, out_ops, out_ops_ptr, ops_cap, needed, kernel_ms, &rc)) return rc;
     if ((rc = shw_check(s, n_pairs))) return rc;
     g_shw_stats[SW_PAIRS] = (double)n_pairs;
     HostClock clk;

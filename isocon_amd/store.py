@@ -114,27 +114,15 @@ class SeqStore(object):
         only, 3 'D' target only) in forward order.  k: None (unbounded), a scalar or one value per pair (negative: unbounded).
         A hit whose distance keeps its path within 256 diagonals is traced on 16-64 bytes per base of t[p], whatever len(q[p]) is; only
         beyond that does a pair need about len(q) * len(t) / 4 bytes, which must fit 1 GiB (path_last_stats() tells the routes)."""
-        q = np.ascontiguousarray(q, dtype=np.uint32)
-        t = np.ascontiguousarray(t, dtype=np.uint32)
-        if len(q) != len(t):
-            raise ValueError("pair arrays differ in length")
+        q, t, kk = self._pair_args(q, t, k, k_is_len=False)
         n = len(q)
-        kk = None if k is None else np.ascontiguousarray(np.broadcast_to(np.asarray(k, dtype=np.int32), q.shape))
         ed = np.full(n, -1, dtype=np.int32)
         ops_ptr = np.zeros(n + 1, dtype=np.uint64)
-        cap = min(256 * n, 1 << 26) + 1024     # generous (untouched pages of np.empty cost nothing): a too-small buffer means tracing again
-        needed = ctypes.c_uint64(0)
-        ms = ctypes.c_float(0)
-        while True:
-            ops = np.empty(cap, dtype=np.uint32)
-            rc = self._L.isocon_ed_path_pairs(self._h, _ptr(q, _lib.u32p), _ptr(t, _lib.u32p), _ptr(kk, _lib.i32p), n, _ptr(ed, _lib.i32p),
-                                              _ptr(ops, _lib.u32p), _ptr(ops_ptr, _lib.u64p), cap, ctypes.byref(needed), ctypes.byref(ms))
-            if rc == _lib.ISOCON_E_CAPACITY:
-                cap = int(needed.value) + 16
-                continue
-            _lib.check(rc, "isocon_ed_path_pairs")
-            out = (ed, ops[:int(ops_ptr[n])], ops_ptr)
-            return out + (ms.value,) if return_ms else out
+        # a generous first buffer (untouched pages of np.empty cost nothing): a too-small one means tracing again
+        ops, ms = self._grown("isocon_ed_path_pairs", (q, t, kk, n, ed),
+                              lambda cap: np.empty(cap, dtype=np.uint32), min(256 * n, 1 << 26) + 1024, (ops_ptr,))
+        out = (ed, ops[:int(ops_ptr[n])], ops_ptr)
+        return out + (ms,) if return_ms else out
 
     def hw_path_pairs(self, q, t, k=None, return_ms=False):
         """edlib.align(q[p], t[p], mode="HW", task="path", k[p]) for a pair list (isocon_hw_path_pairs): (rows int32[n, 5] -- those of
@@ -145,30 +133,14 @@ class SeqStore(object):
         (query, located window) is traced on 16-64 bytes per window column, whatever len(q[p]) is; only beyond that does a hit need
         about len(q) * (end - start + 1) / 4 bytes, which must fit 1 GiB, and is a query of more than 4 096 bases against a window of
         more than 655 360 refused (path_last_stats() tells the routes of the last call)."""
-        q = np.ascontiguousarray(q, dtype=np.uint32)
-        t = np.ascontiguousarray(t, dtype=np.uint32)
-        if len(q) != len(t):
-            raise ValueError("pair arrays differ in length")
+        q, t, kk = self._pair_args(q, t, k)
         n = len(q)
-        # (an id out of range is the library's to refuse)
-        qlen = np.take(np.asarray(self.lens, dtype=np.int64), q, mode="clip") if self.n else np.zeros(n, dtype=np.int64)
-        kk = np.broadcast_to(np.asarray(-1 if k is None else k, dtype=np.int64), q.shape)
-        kk = np.ascontiguousarray(np.where(kk < 0, qlen, kk).clip(max=2 ** 31 - 1), dtype=np.int32)
         rows = np.full((n, 5), -1, dtype=np.int32)
         ops_ptr = np.zeros(n + 1, dtype=np.uint64)
-        cap = min(256 * n, 1 << 26) + 1024     # (as ed_path_pairs)
-        needed = ctypes.c_uint64(0)
-        ms = ctypes.c_float(0)
-        while True:
-            ops = np.empty(cap, dtype=np.uint32)
-            rc = self._L.isocon_hw_path_pairs(self._h, _ptr(q, _lib.u32p), _ptr(t, _lib.u32p), _ptr(kk, _lib.i32p), n, _ptr(rows, _lib.i32p),
-                                              _ptr(ops, _lib.u32p), _ptr(ops_ptr, _lib.u64p), cap, ctypes.byref(needed), ctypes.byref(ms))
-            if rc == _lib.ISOCON_E_CAPACITY:
-                cap = int(needed.value) + 16
-                continue
-            _lib.check(rc, "isocon_hw_path_pairs")
-            out = (rows, ops[:int(ops_ptr[n])], ops_ptr)
-            return out + (ms.value,) if return_ms else out
+        ops, ms = self._grown("isocon_hw_path_pairs", (q, t, kk, n, rows),
+                              lambda cap: np.empty(cap, dtype=np.uint32), min(256 * n, 1 << 26) + 1024, (ops_ptr,))     # (as ed_path_pairs)
+        out = (rows, ops[:int(ops_ptr[n])], ops_ptr)
+        return out + (ms,) if return_ms else out
 
     def hw_locations(self, q, t, k=None, return_ms=False):
         """Every best location of q[p] inside t[p], the `locations` of edlib.align(q[p], t[p], mode="HW", task="path", k[p])
@@ -176,40 +148,43 @@ class SeqStore(object):
         locs[loc_ptr[p]:loc_ptr[p + 1]] = (start, end), one per end column that attains the distance, in ascending order of the end, each
         with the smallest start of that distance; the first is the (start, end) of hw_pairs.  k: a scalar or one value per pair; None or a
         negative value: unbounded (sent as len(q[p])).  The limits are those of hw_pairs: at most four symbols, bands up to 512 diagonals."""
-        q = np.ascontiguousarray(q, dtype=np.uint32)
-        t = np.ascontiguousarray(t, dtype=np.uint32)
-        if len(q) != len(t):
-            raise ValueError("pair arrays differ in length")
+        q, t, kk = self._pair_args(q, t, k)
         n = len(q)
-        # (an id out of range is the library's to refuse)
-        qlen = np.take(np.asarray(self.lens, dtype=np.int64), q, mode="clip") if self.n else np.zeros(n, dtype=np.int64)
-        kk = np.broadcast_to(np.asarray(-1 if k is None else k, dtype=np.int64), q.shape)
-        kk = np.ascontiguousarray(np.where(kk < 0, qlen, kk).clip(max=2 ** 31 - 1), dtype=np.int32)
         ed = np.full(n, -1, dtype=np.int32)
         loc_ptr = np.zeros(n + 1, dtype=np.uint64)
-        cap = 4 * n + 1024
-        needed = ctypes.c_uint64(0)
-        ms = ctypes.c_float(0)
-        while True:
-            locs = np.empty((cap, 2), dtype=np.int32)
-            rc = self._L.isocon_hw_locations(self._h, _ptr(q, _lib.u32p), _ptr(t, _lib.u32p), _ptr(kk, _lib.i32p), n, _ptr(ed, _lib.i32p),
-                                             _ptr(loc_ptr, _lib.u64p), _ptr(locs, _lib.i32p), cap, ctypes.byref(needed), ctypes.byref(ms))
-            if rc == _lib.ISOCON_E_CAPACITY:
-                cap = int(needed.value) + 16
-                continue
-            _lib.check(rc, "isocon_hw_locations")
-            out = (ed, loc_ptr, locs[:int(loc_ptr[n])])
-            return out + (ms.value,) if return_ms else out
+        locs, ms = self._grown("isocon_hw_locations", (q, t, kk, n, ed, loc_ptr),
+                               lambda cap: np.empty((cap, 2), dtype=np.int32), 4 * n + 1024)
+        out = (ed, loc_ptr, locs[:int(loc_ptr[n])])
+        return out + (ms,) if return_ms else out
 
-    def _shw_args(self, q, t, k):
+    def _pair_args(self, q, t, k, k_is_len=True):
+        """the pair list as contiguous arrays; k per pair as int32, None or a negative value meaning len(q[p]) (k_is_len), else k as it came"""
         q = np.ascontiguousarray(q, dtype=np.uint32)
         t = np.ascontiguousarray(t, dtype=np.uint32)
         if len(q) != len(t):
             raise ValueError("pair arrays differ in length")
+        if not k_is_len:
+            return q, t, None if k is None else np.ascontiguousarray(np.broadcast_to(np.asarray(k, dtype=np.int32), q.shape))
         # (an id out of range is the library's to refuse)
         qlen = np.take(np.asarray(self.lens, dtype=np.int64), q, mode="clip") if self.n else np.zeros(len(q), dtype=np.int64)
         kk = np.broadcast_to(np.asarray(-1 if k is None else k, dtype=np.int64), q.shape)
         return q, t, np.ascontiguousarray(np.where(kk < 0, qlen, kk).clip(max=2 ** 31 - 1), dtype=np.int32)
+
+    def _grown(self, name, head, make, cap, tail=()):
+        """the entry `name` over (handle, *head, buffer, *tail, capacity, needed, ms) with buffer = make(capacity), again with room for what it
+        needs (+ 16) while it answers ISOCON_E_CAPACITY -> (buffer, ms).  head, tail: arrays of uint32, int32 or uint64 (or None), and numbers"""
+        types = {np.dtype(np.uint32): _lib.u32p, np.dtype(np.int32): _lib.i32p, np.dtype(np.uint64): _lib.u64p}
+        arg = lambda a: _ptr(a, types[a.dtype]) if isinstance(a, np.ndarray) else a
+        entry = getattr(self._L, name)
+        needed = ctypes.c_uint64(0)
+        ms = ctypes.c_float(0)
+        while True:
+            buf = make(cap)
+            rc = entry(self._h, *map(arg, head), arg(buf), *map(arg, tail), cap, ctypes.byref(needed), ctypes.byref(ms))
+            if rc != _lib.ISOCON_E_CAPACITY:
+                _lib.check(rc, name)
+                return buf, ms.value
+            cap = int(needed.value) + 16
 
     def shw_locations(self, q, t, k=None, return_ms=False):
         """Prefix alignments, edlib.align(q[p], t[p], mode="SHW", k[p]) for a pair list (isocon_shw_locations): the whole of q[p] against a
@@ -218,45 +193,27 @@ class SeqStore(object):
         (0, end)).  k: a scalar or one value per pair; None or a negative value: unbounded (sent as len(q[p]), which h never exceeds).
         At most four symbols; a pair above distance 255 under a threshold beyond it is refused (IsoconError, ISOCON_E_UNSUPPORTED) --
         never a query of at most 255 bases.  shw_last_stats() tells the rounds of the last call."""
-        q, t, kk = self._shw_args(q, t, k)
+        q, t, kk = self._pair_args(q, t, k)
         n = len(q)
         ed = np.full(n, -1, dtype=np.int32)
         end_ptr = np.zeros(n + 1, dtype=np.uint64)
-        cap = 4 * n + 1024
-        needed = ctypes.c_uint64(0)
-        ms = ctypes.c_float(0)
-        while True:
-            ends = np.empty(cap, dtype=np.int32)
-            rc = self._L.isocon_shw_locations(self._h, _ptr(q, _lib.u32p), _ptr(t, _lib.u32p), _ptr(kk, _lib.i32p), n, _ptr(ed, _lib.i32p),
-                                              _ptr(end_ptr, _lib.u64p), _ptr(ends, _lib.i32p), cap, ctypes.byref(needed), ctypes.byref(ms))
-            if rc == _lib.ISOCON_E_CAPACITY:
-                cap = int(needed.value) + 16
-                continue
-            _lib.check(rc, "isocon_shw_locations")
-            out = (ed, end_ptr, ends[:int(end_ptr[n])])
-            return out + (ms.value,) if return_ms else out
+        ends, ms = self._grown("isocon_shw_locations", (q, t, kk, n, ed, end_ptr),
+                               lambda cap: np.empty(cap, dtype=np.int32), 4 * n + 1024)
+        out = (ed, end_ptr, ends[:int(end_ptr[n])])
+        return out + (ms,) if return_ms else out
 
     def shw_path_pairs(self, q, t, k=None, return_ms=False):
         """edlib.align(q[p], t[p], mode="SHW", task="path", k[p]) for a pair list (isocon_shw_path_pairs): (rows int32[n, 2] -- distance or
         -1, first end or -1 --, ops uint32[], ops_ptr uint64[n + 1]); a hit p owns ops[ops_ptr[p]:ops_ptr[p + 1]], the global alignment of
         q[p] against t[p][:end + 1], encoded as in ed_path_pairs.  k and the limits as in shw_locations."""
-        q, t, kk = self._shw_args(q, t, k)
+        q, t, kk = self._pair_args(q, t, k)
         n = len(q)
         rows = np.full((n, 2), -1, dtype=np.int32)
         ops_ptr = np.zeros(n + 1, dtype=np.uint64)
-        cap = min(256 * n, 1 << 26) + 1024     # (as ed_path_pairs)
-        needed = ctypes.c_uint64(0)
-        ms = ctypes.c_float(0)
-        while True:
-            ops = np.empty(cap, dtype=np.uint32)
-            rc = self._L.isocon_shw_path_pairs(self._h, _ptr(q, _lib.u32p), _ptr(t, _lib.u32p), _ptr(kk, _lib.i32p), n, _ptr(rows, _lib.i32p),
-                                               _ptr(ops, _lib.u32p), _ptr(ops_ptr, _lib.u64p), cap, ctypes.byref(needed), ctypes.byref(ms))
-            if rc == _lib.ISOCON_E_CAPACITY:
-                cap = int(needed.value) + 16
-                continue
-            _lib.check(rc, "isocon_shw_path_pairs")
-            out = (rows, ops[:int(ops_ptr[n])], ops_ptr)
-            return out + (ms.value,) if return_ms else out
+        ops, ms = self._grown("isocon_shw_path_pairs", (q, t, kk, n, rows),
+                              lambda cap: np.empty(cap, dtype=np.uint32), min(256 * n, 1 << 26) + 1024, (ops_ptr,))     # (as ed_path_pairs)
+        out = (rows, ops[:int(ops_ptr[n])], ops_ptr)
+        return out + (ms,) if return_ms else out
 
     def qgram_bound_pairs(self, a, b):
         """Lower bounds of ed(a[i], b[i]) from q-gram count profiles (csrc/qgram_mm.hpp) -- the pre-filter of the NN main pass."""

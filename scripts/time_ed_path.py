@@ -62,7 +62,7 @@ for rep in range(5):
 stats = path_last_stats()
 need = np.array([trace_bytes(int(lens[a]), int(lens[b])) for a, b in zip(q, t)], dtype=np.int64)
 launches, held = 1, 0
-for b in need.tolist():          # the host's cut (nw_path_host.inc): consecutive pairs while their stores fit 1 GiB together
+for b in need.tolist():          # the host's cut (nwp_plan.hpp): consecutive pairs while their stores fit 1 GiB together
     if held + b > (1 << 30):
         launches, held = launches + 1, 0
     held += b
