@@ -589,6 +589,35 @@ int isocon_hw_locations(isocon_store *s, const uint32_t *q, const uint32_t *t, c
 int isocon_hw_locations_last_stats(double *out, int32_t cap);
 
 /*
+ * isocon_hw_locations without the limit of 512 diagonals: the same arguments, outputs in the caller's pair order, semantics and capacity
+ * protocol (ISOCON_E_CAPACITY + *needed with out_ed and out_loc_ptr valid and out_locs untouched), with the checks and limits of
+ * isocon_hw_pairs_wide: ids out of range or k[p] < 0 ISOCON_E_ARG, k[p] > 2^20 ISOCON_E_UNSUPPORTED, a store of more than four symbols
+ * ISOCON_E_ALPHABET, a query of more than 4 096 bases against a target of more than 655 360 ISOCON_E_UNSUPPORTED (before any launch);
+ * len(t) - len(q) < -k[p] is a miss.  Nothing is traced, so no pair is refused for its size otherwise.  The first location of a hit is
+ * the (start, end) of isocon_hw_pairs_wide.
+ * Every pair is classed on the host from the two lengths and k[p] as isocon_hw_pairs_wide classes it: the pairs whose own band fits go
+ * through the implementation of isocon_hw_locations as one sub-list in their order (a call without any other pair IS that call), the
+ * others through un-banded kernels that run the recurrence twice and keep nothing per column: a count run (distance, first end, number
+ * of ends; an exclusive scan of the counts gives the row pointers) and a fill run that lists the ends.  A query of at most 256 bases
+ * takes one LANE of a kernel that holds the whole query in registers (1, 2 or 4 words of 64 rows), a longer one a wavefront (64 rows
+ * per lane).  The start of an end with distance h <= 255 comes from the start pass of isocon_hw_locations on diagonals [-h, h], that of
+ * an end with a larger distance from an un-banded start pass, one wavefront per end.  *kernel_ms sums all of it.
+ */
+int isocon_hw_locations_wide(isocon_store *s, const uint32_t *q, const uint32_t *t, const int32_t *k, uint64_t n_pairs,
+                             int32_t *out_ed /* n_pairs */, uint64_t *out_loc_ptr /* n_pairs + 1 */, int32_t *out_locs /* cap x 2 */,
+                             uint64_t cap, uint64_t *needed, float *kernel_ms);
+
+/*
+ * What the calling thread's last isocon_hw_locations_wide call did (no counterpart in the reference; tests and timing scripts): out[0]
+ * pairs, out[1] pairs that went through isocon_hw_locations, out[2] wide pairs, out[3] hits, out[4] locations (both of all pairs),
+ * out[5..7] wide pairs on the lane-per-pair kernel with 1, 2, 4 query words, out[8] wide pairs on the wavefront-per-pair kernel,
+ * out[9] (pair, end) entries of wide pairs whose start came from the banded start pass, out[10] from the un-banded one, out[11]
+ * launches for the wide pairs (0 when the call had none), out[12] kernel milliseconds.  Writes min(cap, 13) values and returns that
+ * number.
+ */
+int isocon_hw_locations_wide_last_stats(double *out, int32_t cap);
+
+/*
  * Prefix alignments of a pair list: edlib.align(q, t, mode="SHW", k) -- the whole query against a PREFIX of the target (a primer that
  * must sit at the read's start; on reversed strings, at its end).  With D the global matrix of query q[p] (length P) and target t[p]
  * (length n) -- D[0][j] = j, D[i][0] = i -- h = min over columns 1 <= j <= n of D[P][j] = min over j of ed(q, t[0..j)): out_ed[p] = h if

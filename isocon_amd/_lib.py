@@ -121,6 +121,8 @@ SYMBOLS = {
     "isocon_hw_path_pairs": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, i32p, ctypes.c_uint64, i32p, u32p, u64p, ctypes.c_uint64, u64p, f32p]),
     "isocon_hw_locations": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, i32p, ctypes.c_uint64, i32p, u64p, i32p, ctypes.c_uint64, u64p, f32p]),
     "isocon_hw_locations_last_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.c_int32]),
+    "isocon_hw_locations_wide": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, i32p, ctypes.c_uint64, i32p, u64p, i32p, ctypes.c_uint64, u64p, f32p]),
+    "isocon_hw_locations_wide_last_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.c_int32]),
     "isocon_shw_locations": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, i32p, ctypes.c_uint64, i32p, u64p, i32p, ctypes.c_uint64, u64p, f32p]),
     "isocon_shw_path_pairs": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, i32p, ctypes.c_uint64, i32p, u32p, u64p, ctypes.c_uint64, u64p, f32p]),
     "isocon_shw_last_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.c_int32]),

@@ -29,10 +29,11 @@ struct HwfIn {
 // All passes of one mode for the wavefront's pair.  text(s, wl, wh): the 32 text bits of columns s .. s + 31 (s a multiple of 32,
 // wave-uniform).  bound: LDS, hwf_bound_words(ncols) words when the query has more than one pass.  TRACE: store = the pair's trace
 // store, whose head takes the last column; keep_cols: every column is kept as well.  The results are those of the query's last row,
-// the same in every lane.
-template <int MODE, class Text>
+// the same in every lane.  ENDS: sink(score, col) after every column of the query's last row, in the lane that owns that row.
+struct HwfNoSink { __device__ __forceinline__ void operator()(int32_t, int32_t) const {} };
+template <int MODE, class Text, class Sink = HwfNoSink>
 __device__ __forceinline__ void hwf_run(const DevStore &S, uint32_t q, int32_t m, int32_t ncols, int32_t h, Text text, uint32_t *bound,
-                                        ulonglong2 *store, bool keep_cols, int32_t &r_score, int32_t &r_best, int32_t &r_col)
+                                        ulonglong2 *store, bool keep_cols, int32_t &r_score, int32_t &r_best, int32_t &r_col, Sink sink = Sink())
 {
     const int lane = threadIdx.x;
     const uint64_t *planes = S.planes;
@@ -59,7 +60,7 @@ __device__ __forceinline__ void hwf_run(const DevStore &S, uint32_t q, int32_t m
             int32_t ch, hin;
             if (lane == 0) {
                 ch = (int32_t)(((wl >> (s & 31)) & 1u) | (((wh >> (s & 31)) & 1u) << 1));
-                hin = pass == 0 ? (MODE == HWF_LOCATE ? 0 : 1) : (s < ncols ? hwf_bound_get(bound[s >> 4], s) : 0);
+                hin = pass == 0 ? (MODE == HWF_LOCATE || MODE == HWF_ENDS ? 0 : 1) : (s < ncols ? hwf_bound_get(bound[s >> 4], s) : 0);
             } else {
                 ch = hwf_packed_base(recv);
                 hin = hwf_packed_delta(recv);
@@ -73,6 +74,7 @@ __device__ __forceinline__ void hwf_run(const DevStore &S, uint32_t q, int32_t m
                     if (tp) tp[(size_t)s * nbl + lane] = make_ulonglong2(L.Pv, ph);
                     if (col == ncols - 1 && fin) fin[blk] = L.Pv;
                 }
+                if (MODE == HWF_ENDS && blk == ((m - 1) >> 6)) sink(L.score, col);
                 if (lane == 63 && pass + 1 < passes) {
                     bw = hwf_bound_add(bw, col, hout);
                     if (hwf_bound_full(col, ncols)) { bound[col >> 4] = bw; bw = 0; }

@@ -11,13 +11,15 @@
 //   TRACE   query against t[start..end], top-row delta +1; every column and block keeps its new Pv (bit r: the vertical step into row
 //           r + 1 of the block is optimal) and its Ph (bit r: the horizontal step into that row is), the walk from the end cell prefers
 //           the query-only step ('I'), then the target-only one ('D'), then the diagonal.
+//   ENDS    the recurrence of LOCATE (top row free, every column) without its bookkeeping: the caller reads the last row's value after
+//           every column (hw_rows.hpp: the columns attaining the distance are counted, then listed).
 // The same header is compiled by g++ for tests/emul/hw_full_emul.cpp (64 emulated lanes in lock step, against the oracle).
 #pragma once
 #include "hw_core.hpp"
 
 namespace isocon {
 
-enum { HWF_LOCATE = 0, HWF_START = 1, HWF_TRACE = 2 };
+enum { HWF_LOCATE = 0, HWF_START = 1, HWF_TRACE = 2, HWF_ENDS = 3 };
 
 struct HwfLane {
     uint64_t nlo, nhi, valid;          // the block's rows: complemented plane words, and which rows the query has

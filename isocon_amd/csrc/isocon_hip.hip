@@ -33,6 +33,7 @@
 #include "hw_loc.hpp"
 #include "shw.hpp"
 #include "hw_full.hpp"
+#include "hw_rows.hpp"
 #include "hw_graph.hpp"
 #include "end_inv.hpp"
 #include "nw_path.hpp"
@@ -111,7 +112,7 @@ struct HeldHits { uint64_t store_serial = 0; uint64_t rows = 0; };
 // hipMalloc/hipFree (tens of ms for the multi-GB trace scratch) every time.
 struct ScratchPool {
     struct Slot { void *p = nullptr; size_t cap = 0; };
-    Slot slots[192];
+    Slot slots[208];
     BoundTag bound_tag;
     HeldHits held_hits;
     MsaBuilt msa;
@@ -146,6 +147,7 @@ enum {
     SLOT_MSA_IN, SLOT_MSA_OUT, SLOT_MSA_DEG, SLOT_MSA_COUNTS, SLOT_MSA_MAJ, SLOT_MSA_FLAGS, SLOT_MSA_TOT, SLOT_MSA_NCAND, SLOT_MSA_LEN, SLOT_MSA_OFF, SLOT_MSA_PACKED, SLOT_MSA_ROWS, SLOT_MSA_OPS, SLOT_MSA_OPTR, SLOT_MSA_LONGEST, SLOT_MSA_WIDTH, SLOT_MSA_CSLOT, SLOT_MSA_LTOT, SLOT_MSA_WIDE, SLOT_MSA_PROW, SLOT_MSA_PCOL, SLOT_MSA_PPTR, SLOT_MSA_PBYTES, SLOT_MSA_PART, SLOT_MSA_FIRST, SLOT_MSA_LM, SLOT_MSA_SBASE, SLOT_MSA_NCOLS, SLOT_MSA_MOFF, SLOT_MSA_CBASE, SLOT_MSA_CBP, SLOT_MSA_CBC, SLOT_MSA_CBR, SLOT_MSA_WIDX, SLOT_MSA_KEYS, SLOT_MSA_LEFT,
     SLOT_HW_Q, SLOT_HW_T, SLOT_HW_K, SLOT_HW_OUT, SLOT_HW_TRACE, SLOT_HW_CTR, SLOT_HW_TILEQ, SLOT_HW_LANES, SLOT_HW_PQ, SLOT_HW_KEY, SLOT_HW_HIST, SLOT_HW_CURSOR, SLOT_HW_TBASE, SLOT_HW_CLS,
     SLOT_HWL_THR, SLOT_HWL_CNT, SLOT_HWL_PTR, SLOT_HWL_EQ, SLOT_HWL_ET, SLOT_HWL_EH, SLOT_HWL_EHE, SLOT_HWL_LOCS, SLOT_SHW_ENTER,
+    SLOT_HWLW_Q, SLOT_HWLW_T, SLOT_HWLW_K, SLOT_HWLW_HE, SLOT_HWLW_CNT, SLOT_HWLW_PTR, SLOT_HWLW_LIST, SLOT_HWLW_ULIST, SLOT_HWLW_FLAGS,
     SLOT_HWG_CD, SLOT_HWG_TOT, SLOT_HWG_FIRST, SLOT_HWG_CTR, SLOT_HWG_VALUE, SLOT_HWG_ROWCNT, SLOT_HWG_ROWPTR, SLOT_HWG_COLS, SLOT_HWG_ED,
     SLOT_EINV_LO, SLOT_EINV_TOT, SLOT_EINV_FIRST, SLOT_EINV_CTR, SLOT_EINV_BEST, SLOT_EINV_SURV, SLOT_EINV_ROWCNT, SLOT_EINV_ROWPTR, SLOT_EINV_COLS,
     SLOT_PACK_ASCII, SLOT_PACK_OFF, SLOT_PACK_BAD, SLOT_PACK_HIST, SLOT_PACK_FLAGS, SLOT_EB_A, SLOT_EB_B, SLOT_EB_K, SLOT_EB_OUT, SLOT_EB_ROWS, SLOT_SCAN_TMP, SLOT_SCAN_SUMS, SLOT_SCAN_TMP_SIDE, SLOT_SCAN_SUMS_SIDE,
@@ -156,7 +158,7 @@ enum {
     SLOT_NWB_TRACE, SLOT_NWB_SLOTS, SLOT_NWB_WOFF, SLOT_NWB_WCOLS, SLOT_NWB_WLANES,
     SLOT_COUNT
 };
-static_assert(SLOT_COUNT <= 192, "ScratchPool::slots too small");
+static_assert(SLOT_COUNT <= 208, "ScratchPool::slots too small");
 
 // One pool per process (one process drives one GPU): scratch outlives the individual stores, because the Python
 // wrappers create a fresh store per call (the reference's functions are stateless).
@@ -1109,6 +1111,7 @@ static int copy_last_stats(const double *stats, int count, double *out, int32_t 
 #include "hw_host.inc"
 #include "hw_loc_host.inc"
 #include "hw_full_host.inc"
+#include "hw_loc_wide_host.inc"
 #include "hw_graph_host.inc"
 #include "end_inv_host.inc"
 #include "nw_path_host.inc"

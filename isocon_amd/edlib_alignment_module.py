@@ -196,11 +196,13 @@ def edlib_traceback_infix_all(x, y, k=1):
     distance (SeqStore.hw_locations) -- what primer, barcode, poly-A and repeat searches ask.  locations[0] is the one location
     edlib_traceback_infix reports, and the cigar belongs to it (edlib's convention; SeqStore.hw_path_pairs).  k None or negative:
     unbounded.  Above k, and for an empty x or y: (-1, [], None).  GPU only and at most four distinct symbols, like
-    edlib_traceback_infix; a pair whose band max(len(y) - len(x), 0) + 2 k + 1 exceeds 512 diagonals raises IsoconError."""
+    edlib_traceback_infix.  Any k is answered (SeqStore.hw_locations(wide=True)): a pair whose band max(len(y) - len(x), 0) + 2 k + 1
+    fits 512 diagonals runs on the banded kernels, any other -- a 30-base primer in a 2 500-base read, any query of 256 bases or more
+    with k=None -- on the un-banded ones; the limits left are those of edlib_traceback_infix."""
     kk = None if k is None or k < 0 else [int(k)]
     st = SeqStore([x, y])
     try:
-        ed, loc_ptr, locs = st.hw_locations([0], [1], kk)
+        ed, loc_ptr, locs = st.hw_locations([0], [1], kk, wide=True)
         ops = st.hw_path_pairs([0], [1], kk)[1] if ed[0] >= 0 else None
     finally:
         st.close()

@@ -142,20 +142,28 @@ class SeqStore(object):
         out = (rows, ops[:int(ops_ptr[n])], ops_ptr)
         return out + (ms,) if return_ms else out
 
-    def hw_locations(self, q, t, k=None, return_ms=False):
+    def hw_locations(self, q, t, k=None, return_ms=False, wide=False):
         """Every best location of q[p] inside t[p], the `locations` of edlib.align(q[p], t[p], mode="HW", task="path", k[p])
         (isocon_hw_locations): (ed int32[n] -- distance or -1 --, loc_ptr uint64[n + 1], locs int32[L, 2]); a hit p owns the rows
         locs[loc_ptr[p]:loc_ptr[p + 1]] = (start, end), one per end column that attains the distance, in ascending order of the end, each
         with the smallest start of that distance; the first is the (start, end) of hw_pairs.  k: a scalar or one value per pair; None or a
-        negative value: unbounded (sent as len(q[p])).  The limits are those of hw_pairs: at most four symbols, bands up to 512 diagonals."""
+        negative value: unbounded (sent as len(q[p])).  The limits are those of hw_pairs: at most four symbols, bands up to 512 diagonals.
+        wide: isocon_hw_locations_wide -- pairs whose band max(len_t - len_q, 0) + 2 k + 1 exceeds 512 diagonals are answered too
+        (un-banded kernels, the limits of hw_pairs(wide=True) without its trace budget) instead of refused; the pairs within the band
+        get the same rows through the same kernels (hw_locations_wide_last_stats() tells the routes of the last call)."""
         q, t, kk = self._pair_args(q, t, k)
         n = len(q)
         ed = np.full(n, -1, dtype=np.int32)
         loc_ptr = np.zeros(n + 1, dtype=np.uint64)
-        locs, ms = self._grown("isocon_hw_locations", (q, t, kk, n, ed, loc_ptr),
+        locs, ms = self._grown("isocon_hw_locations_wide" if wide else "isocon_hw_locations", (q, t, kk, n, ed, loc_ptr),
                                lambda cap: np.empty((cap, 2), dtype=np.int32), 4 * n + 1024)
         out = (ed, loc_ptr, locs[:int(loc_ptr[n])])
         return out + (ms,) if return_ms else out
+
+    @staticmethod
+    def hw_locations_wide_last_stats():
+        """what this thread's most recent hw_locations(wide=True) call did (the module's hw_locations_wide_last_stats)"""
+        return hw_locations_wide_last_stats()
 
     def _pair_args(self, q, t, k, k_is_len=True):
         """the pair list as contiguous arrays; k per pair as int32, None or a negative value meaning len(q[p]) (k_is_len), else k as it came"""
@@ -728,6 +736,17 @@ def hw_locations_last_stats():
     keys = ("pairs", "hits", "locations", "host_cuts") + tuple(
         "%s_w%d" % (name, w) for name in ("locate_tiles", "ends_tiles", "starts_tiles") for w in (1, 2, 4, 8))
     return {key: int(v) for key, v in zip(keys, out)}
+
+
+def hw_locations_wide_last_stats():
+    """what this thread's most recent hw_locations(wide=True) call did (isocon_hw_locations_wide_last_stats, include/isocon_hip.h): pairs,
+    narrow (through isocon_hw_locations) and wide pairs, hits and locations of all of them, wide pairs per kernel (one lane per pair with
+    1, 2, 4 query words; one wavefront per pair), (pair, end) entries per start pass (banded, un-banded), launches for the wide pairs and
+    kernel milliseconds"""
+    out = (ctypes.c_double * 13)()
+    _lib.load().isocon_hw_locations_wide_last_stats(out, 13)
+    keys = ("pairs", "narrow", "wide", "hits", "locations", "rows_w1", "rows_w2", "rows_w4", "wave", "starts_banded", "starts_unbanded", "launches")
+    return dict({key: int(v) for key, v in zip(keys, out)}, kernel_ms=float(out[12]))
 
 
 def shw_last_stats():
